@@ -1,7 +1,7 @@
 """bench.py -- GPV-1 train-step throughput on MI355X (BASELINE.json metric: images/sec/node, train
 step, 480x640, bs32/GPU; workload = configs[1]: CocoCaptioning-only train step, bf16, one rank per GPU).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]        (N>1: launched by torch.distributed.run)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run)
 
 A "step" is one full iteration of the reference hot loop (exp/gpv/train_distr.py:399-428):
 encode_answers -> GPV.forward (ResNet-50 -> DETR 6+6 -> RoI head -> BERT -> co-attention x3 -> text
@@ -9,10 +9,13 @@ decoder x3 -> vocabulary logits V=10000 -> caption CE) -> backward -> gradient a
 clip_grad_norm_(DETR, 0.1) -> AdamW.  Dropout 0.1 is ON (train mode).  Synthetic data (seeded),
 random-init weights; inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0) with the contract fields + "roofline" (dominant kernel: the implicit-GEMM
-convolution of the backbone, timed live with HIP events on the launch stream inside the timed region)
-+ "roofline_attention" (encoder attention core against the dense bf16 MFMA peak) + "cpu_baseline" (the CPU
-oracle's forward+backward and greedy decode on this host, bounded sample, N=1 only).
+A plain run sets up, warms up, times K steps and prints ONE JSON line (rank 0) with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --dump-outputs DIR writes what the last
+timed step computed (dump_outputs).  --full adds everything else, each after the timed region:
+"roofline" (dominant kernel: the implicit-GEMM convolution of the backbone, timed live with HIP events on the
+launch stream) + "roofline_attention" (encoder attention core against the dense bf16 MFMA peak) + the ragged,
+extra-config, precise and greedy-decode figures + "cpu_baseline" (the CPU oracle's forward+backward and greedy
+decode on this host, bounded sample, N=1 only); the --no-* switches leave parts of it out.
 --gpus N without a launcher starts the N ranks itself (torch.distributed.run on 127.0.0.1).
 """
 import argparse
@@ -58,8 +61,8 @@ def live_conv_traffic():
     try:
         for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
             d = dirs[counter] = os.path.join(tmp, counter)
-            cmd = [exe, '--pmc', counter, '--output-format', 'csv', '-d', d, '-o', 'r', '--', sys.executable, os.path.abspath(__file__), '--no-cpu-baseline',
-                   '--no-decode', '--no-ragged', '--no-extra', '--no-traffic', '--steps', '4', '--warmup', '3']
+            cmd = [exe, '--pmc', counter, '--output-format', 'csv', '-d', d, '-o', 'r', '--', sys.executable, os.path.abspath(__file__), '--full',
+                   '--no-cpu-baseline', '--no-decode', '--no-ragged', '--no-extra', '--no-traffic', '--steps', '4', '--warmup', '3']
             r = subprocess.run(cmd, cwd='/tmp', env=env, capture_output=True, text=True, timeout=900)
             if r.returncode != 0:
                 return {'error': '%s pass: rc %d: %s' % (counter, r.returncode, (r.stderr or r.stdout)[-300:])}
@@ -282,6 +285,79 @@ def attention_roofline(dev, B):
             'note': 'dh = 32: 2 MFMAs per 256 scores against ~12 VALU instructions per score -- the core is VALU-bound, see DESIGN.md'}
 
 
+def conv_roofline(model, args, world, prof, prof_timed):
+    """--full: roofline of the dominant kernel (implicit-GEMM conv, backbone fwd+bwd) from the conv launches timed after the timed
+    region (prof) and the brackets recorded inside it (prof_timed)"""
+    alg = conv_algorithmic(model, args.batch)
+    ms = {'conv_fwd': 0.0, 'conv_bwd': 0.0}
+    for tag, a, b in prof:
+        ms[tag] += a.elapsed_time(b)
+    conv_ms = (ms['conv_fwd'] + ms['conv_bwd']) / args.steps
+    launches = alg['fwd_launches'] + alg['bwd_launches']
+    bytes_step = alg['fwd_bytes'] + alg['bwd_bytes']
+    flops_step = alg['fwd_flops'] + alg['bwd_flops']
+    ach_gbs = bytes_step / (conv_ms * 1e-3) / 1e9
+    # HBM traffic per launch from the PMC counters (FETCH_SIZE x2 + WRITE_SIZE, tools/pmc_traffic.py): cannot be collected
+    # inside a timed run, so it is the committed measurement of this same command (tools/pmc_traffic.py ->
+    # profiles/rNN_pmc_conv_traffic.json, per-launch = a pass's bytes / the reference's 135 convolutions); null if that file is
+    # missing or does not hold whole passes.
+    traffic = None
+    traffic_source = None
+    traffic_live = None
+    if not (args.no_traffic or args.no_extra) and world == 1 and args.batch == BATCH:
+        traffic_live = live_conv_traffic()
+        if traffic_live is not None and 'traffic_bytes_per_launch' in traffic_live:
+            traffic = traffic_live['traffic_bytes_per_launch']
+            traffic_source = ('live: two rocprofv3 --pmc passes (FETCH_SIZE, then WRITE_SIZE) of `python bench.py --full --steps 4 --warmup 3` run by THIS process after the timed region '
+                              '(%d whole passes of the body; FETCH_SIZE x 2 on gfx950, units and corrections: tools/pmc_traffic.py)'
+                              % int(traffic_live['passes_profiled']))
+    try:
+        if traffic is not None:
+            raise OSError('live')
+        import glob
+        latest = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'r*_pmc_conv_traffic.json')))[-1]
+        pm = json.load(open(latest))
+        passes = pm['passes_profiled']                # whole forward + backward passes of the body in the profiled run (stem launches)
+        if passes >= 1 and passes == int(passes) and pm['conv_launches_fetch_pass'] % int(passes) == 0 \
+                and pm['conv_launches_fetch_pass'] == pm['conv_launches_write_pass'] and args.batch == BATCH:
+            traffic = pm['traffic_bytes_per_launch']
+            traffic_source = 'profiles/%s (committed PMC measurement of this command, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE: not collected by this run)' % os.path.basename(latest)
+    except (OSError, KeyError, ValueError, IndexError):
+        pass
+    roof = {'bound': 'hbm', 'achieved': ach_gbs, 'peak': 8000.0, 'unit': 'GB/s', 'frac': ach_gbs / 8000.0, 'traffic': traffic,
+            'traffic_source': traffic_source,
+            'traffic_over_algorithmic': None if traffic is None else traffic / (bytes_step / launches),
+            'traffic_live_error': None if (traffic_live is None or 'error' not in traffic_live) else traffic_live['error'],
+            'frac_mixed_per_conv_bound': alg['mixed_bound_s'] / (conv_ms * 1e-3),      # sum over launches of max(bytes / 8 TB/s, flops / 2.5 PF) / measured time
+            'kernel': 'c1s_kernel (streaming 1x1) / c3r_kernel (streaming 3x3) / stem_pool_kernel / c1d_kernel / glds_wgrad_group_kernel + wg8_group_kernel + wg8h_group_kernel (the 42 weight gradients as one grouped call per stage) / glds_kernel<OP_CONV> / pipe_kernel<OP_CONV> / pipe_conv1x1_kernel / conv1x1_kernel / gemm_kernel<OP_CONV> (NHWC conv fwd/dgrad/wgrad, ResNet-50 body)',
+            'launches_per_step': launches, 'avg_launch_us': conv_ms * 1e3 / launches,
+            'algorithmic_bytes_per_launch': bytes_step / launches,
+            'fwd_ms': ms['conv_fwd'] / args.steps, 'bwd_ms': ms['conv_bwd'] / args.steps,
+            'timed_region_brackets_ms': {'backbone_fwd_graph_with_bert_branch': sum(a.elapsed_time(b) for t_, a, b in prof_timed if t_ == 'conv_fwd') / args.steps,
+                                         'backbone_bwd_graph_with_wgrad_branch': sum(a.elapsed_time(b) for t_, a, b in prof_timed if t_ == 'conv_bwd') / args.steps,
+                                         'graph_f2_after_backbone_to_criterion_inputs': sum(a.elapsed_time(b) for t_, a, b in prof_timed if t_ == 'graph_f2') / args.steps,
+                                         'graph_b1_backward_down_to_backbone': sum(a.elapsed_time(b) for t_, a, b in prof_timed if t_ == 'graph_b1') / args.steps},
+            'mfma_tflops': flops_step / (conv_ms * 1e-3) / 1e12, 'mfma_frac_of_2500': flops_step / (conv_ms * 1e-3) / 2.5e15}
+    return roof
+
+
+DUMP_SAMPLE = 1 << 20        # positions of the flat parameter buffer that --dump-outputs writes (4 MB in fp32)
+
+
+def dump_outputs(out_dir, tr, loss):
+    """--dump-outputs DIR: what the last timed step leaves its caller, as DIR/<name>.npy (float32) -- the loss train_step returned,
+    and the fp32 master weights AdamW wrote (the trainer's flat buffer P) at a fixed seeded sample of positions, the same in every
+    run and every build.  The gradient buffer is not written: between two runs of the same build with the default arguments its
+    DETR part differs by about its own norm (relative L2 0.8 - 1.3 measured on an MI355X), so it could not tell two builds apart."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(20240613)
+    idx = torch.randint(0, tr.total, (min(DUMP_SAMPLE, tr.total),), generator=g).sort().values.to(tr.P.device)
+    arrays = {'loss': loss.detach().float().reshape(1), 'params_sample': tr.P[idx]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy().astype(np.float32))
+
+
 def self_launch(args):
     """python bench.py --gpus N without a launcher: start N ranks on this node (the reference spawns its own ranks too,
     exp/gpv/train_distr.py:488-493) through torch.distributed.run and pass its exit code on"""
@@ -479,6 +555,9 @@ def main():
     ap.add_argument('--no-extra', action='store_true', help='skip BASELINE configs[3] (beam 5, bs64) and configs[4] (detection-only bs64)')
     ap.add_argument('--no-traffic', action='store_true', help='do not run the two rocprofv3 --pmc passes of this command (roofline.traffic then comes from the committed profile)')
     ap.add_argument('--soak', type=int, default=0, help='after the timed region: this many more graphed steps (soak of the hipGraph replay path)')
+    ap.add_argument('--full', action='store_true', help='after the timed region also measure the rooflines, the ragged / extra / precise / '
+                                                         'greedy-decode figures and the CPU baseline (a plain run measures the train step only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (dump_outputs)')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args))
@@ -562,7 +641,7 @@ def main():
         dist.barrier()
         _note_sync()
     torch.cuda.synchronize()
-    bbm.PROF = []
+    bbm.PROF = [] if args.full else None              # backbone brackets: for the --full roofline only
     if multi:
         tr.comm_prof = []
     import gpv1_amd.train as trm
@@ -582,6 +661,8 @@ def main():
     host_prof, trm.HOST_PROF = trm.HOST_PROF, None
     trm.HOST_PROF = host_prof if False else None
     prof_timed, bbm.PROF = bbm.PROF, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, loss)       # before anything below runs more steps on the trainer
     # Convolution time for the roofline.  In the timed region the backbone graphs also carry other kernels as parallel branches
     # (train.GraphedBody: the frozen BERT beside the forward convolutions, the model body's weight-gradient GEMMs beside the
     # backward ones), so their brackets are conv + 1-3 ms of other kernels' work sharing the CUs (reported as
@@ -636,57 +717,6 @@ def main():
         torch.cuda.synchronize()
         soak = {'steps': args.soak, 'ms_per_step': (time.perf_counter() - t0s) / args.soak * 1e3, 'final_loss': float(ls.detach()),
                 'finite': bool(torch.isfinite(ls.detach()))}
-    # ---- roofline of the dominant kernel (implicit-GEMM conv, backbone fwd+bwd), live HIP events ----
-    alg = conv_algorithmic(model, args.batch)
-    ms = {'conv_fwd': 0.0, 'conv_bwd': 0.0}
-    for tag, a, b in prof:
-        ms[tag] += a.elapsed_time(b)
-    conv_ms = (ms['conv_fwd'] + ms['conv_bwd']) / args.steps
-    launches = alg['fwd_launches'] + alg['bwd_launches']
-    bytes_step = alg['fwd_bytes'] + alg['bwd_bytes']
-    flops_step = alg['fwd_flops'] + alg['bwd_flops']
-    ach_gbs = bytes_step / (conv_ms * 1e-3) / 1e9
-    # HBM traffic per launch from the PMC counters (FETCH_SIZE x2 + WRITE_SIZE, MI355X_MICROARCH.md): cannot be collected
-    # inside a timed run, so it is the committed measurement of this same command (tools/pmc_traffic.py ->
-    # profiles/rNN_pmc_conv_traffic.json, per-launch = a pass's bytes / the reference's 135 convolutions); null if that file is
-    # missing or does not hold whole passes.
-    traffic = None
-    traffic_source = None
-    traffic_live = None
-    if not (args.no_traffic or args.no_extra) and world == 1 and args.batch == BATCH:
-        traffic_live = live_conv_traffic()
-        if traffic_live is not None and 'traffic_bytes_per_launch' in traffic_live:
-            traffic = traffic_live['traffic_bytes_per_launch']
-            traffic_source = ('live: two rocprofv3 --pmc passes (FETCH_SIZE, then WRITE_SIZE) of `python bench.py --steps 4 --warmup 3` run by THIS process after the timed region '
-                              '(%d whole passes of the body; FETCH_SIZE x 2 on gfx950, units and corrections as /opt/skills/guides/MI355X_MICROARCH.md; tools/pmc_traffic.py)'
-                              % int(traffic_live['passes_profiled']))
-    try:
-        if traffic is not None:
-            raise OSError('live')
-        import glob
-        latest = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'r*_pmc_conv_traffic.json')))[-1]
-        pm = json.load(open(latest))
-        passes = pm['passes_profiled']                # whole forward + backward passes of the body in the profiled run (stem launches)
-        if passes >= 1 and passes == int(passes) and pm['conv_launches_fetch_pass'] % int(passes) == 0 \
-                and pm['conv_launches_fetch_pass'] == pm['conv_launches_write_pass'] and args.batch == BATCH:
-            traffic = pm['traffic_bytes_per_launch']
-            traffic_source = 'profiles/%s (committed PMC measurement of this command, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE: not collected by this run)' % os.path.basename(latest)
-    except (OSError, KeyError, ValueError, IndexError):
-        pass
-    roof = {'bound': 'hbm', 'achieved': ach_gbs, 'peak': 8000.0, 'unit': 'GB/s', 'frac': ach_gbs / 8000.0, 'traffic': traffic,
-            'traffic_source': traffic_source,
-            'traffic_over_algorithmic': None if traffic is None else traffic / (bytes_step / launches),
-            'traffic_live_error': None if (traffic_live is None or 'error' not in traffic_live) else traffic_live['error'],
-            'frac_mixed_per_conv_bound': alg['mixed_bound_s'] / (conv_ms * 1e-3),      # sum over launches of max(bytes / 8 TB/s, flops / 2.5 PF) / measured time
-            'kernel': 'c1s_kernel (streaming 1x1) / c3r_kernel (streaming 3x3) / stem_pool_kernel / c1d_kernel / glds_wgrad_group_kernel + wg8_group_kernel + wg8h_group_kernel (the 42 weight gradients as one grouped call per stage) / glds_kernel<OP_CONV> / pipe_kernel<OP_CONV> / pipe_conv1x1_kernel / conv1x1_kernel / gemm_kernel<OP_CONV> (NHWC conv fwd/dgrad/wgrad, ResNet-50 body)',
-            'launches_per_step': launches, 'avg_launch_us': conv_ms * 1e3 / launches,
-            'algorithmic_bytes_per_launch': bytes_step / launches,
-            'fwd_ms': ms['conv_fwd'] / args.steps, 'bwd_ms': ms['conv_bwd'] / args.steps,
-            'timed_region_brackets_ms': {'backbone_fwd_graph_with_bert_branch': sum(a.elapsed_time(b) for t_, a, b in prof_timed if t_ == 'conv_fwd') / args.steps,
-                                         'backbone_bwd_graph_with_wgrad_branch': sum(a.elapsed_time(b) for t_, a, b in prof_timed if t_ == 'conv_bwd') / args.steps,
-                                         'graph_f2_after_backbone_to_criterion_inputs': sum(a.elapsed_time(b) for t_, a, b in prof_timed if t_ == 'graph_f2') / args.steps,
-                                         'graph_b1_backward_down_to_backbone': sum(a.elapsed_time(b) for t_, a, b in prof_timed if t_ == 'graph_b1') / args.steps},
-            'mfma_tflops': flops_step / (conv_ms * 1e-3) / 1e12, 'mfma_frac_of_2500': flops_step / (conv_ms * 1e-3) / 2.5e15}
     out = {'metric': 'images/sec/node (train step, 480x640, bs32/GPU)', 'value': world * args.batch * args.steps / elapsed,
            'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
            'ms_per_step': elapsed / args.steps * 1e3, 'host_ms_per_step': host_s / args.steps * 1e3,
@@ -695,26 +725,28 @@ def main():
            'config': {'workload': 'GPV-1 (ResNet-50 + 6+6 DETR layers, 100 queries, RoI head, BERT-base, 3 co-attention, '
                                   '3 text-decoder layers, V=10000) CocoCaptioning-only train step, dropout 0.1, AdamW',
                       'global_batch': world * args.batch, 'image': '480x640', 'caption_tokens': 20,
-                      'parallelism': f'dp{world}', 'final_loss': float(loss.detach())},
-           'roofline': roof}
+                      'parallelism': f'dp{world}', 'final_loss': float(loss.detach())}}
+    if args.full:
+        out['roofline'] = conv_roofline(model, args, world, prof, prof_timed)
     out['graphs'] = {'enabled': bool(tr.graphs), 'graph_steps': tr.graph_steps, 'eager_steps': tr.eager_steps}
     if graphs_note:
         out['graphs']['error'] = graphs_note
-    out['roofline_attention'] = attention_roofline(dev, args.batch)
+    if args.full:
+        out['roofline_attention'] = attention_roofline(dev, args.batch)
     if comm is not None:
         out['comm'] = comm
     if soak is not None:
         out['soak'] = soak
-    if world == 1 and not args.no_ragged and args.batch == BATCH:
+    if args.full and world == 1 and not args.no_ragged and args.batch == BATCH:
         out['ragged'] = ragged_bench(model, tr, dev, rank)
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         out['extra'] = extra_configs(model, tr, dev, rank)
         out['extra']['input_pipeline_bs32'] = input_pipeline_bench(dev)
-    if world == 1 and not args.no_decode:
+    if args.full and world == 1 and not args.no_decode:
         out['greedy_decode'] = greedy_decode_bench(model, dev)
-    if world == 1 and not args.no_extra and args.batch == BATCH:
+    if args.full and world == 1 and not args.no_extra and args.batch == BATCH:
         out['extra']['precise_train_step_ms'] = precise_bench(model, tr, dev, rank)       # (last: it retires every captured graph)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             out['cpu_baseline'] = cpu_baseline(model)
         except Exception as e:                                     # the baseline must never sink the bench line

@@ -7,7 +7,7 @@ VAR=${VAR:-GPV_WG8H}; A=${A:-0}; B=${B:-1}
 for r in 1 2 3; do
   for v in $A $B; do
     echo -n "$VAR=$v: "
-    env GPV_TUNING_LIB=1 $VAR=$v timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decode --no-ragged --no-extra 2>/dev/null | \
+    env GPV_TUNING_LIB=1 $VAR=$v timeout 600 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-decode --no-ragged --no-extra 2>/dev/null | \
       python -c "import sys, json; d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f ms  frac %.4f' % (d['ms_per_step'], d['roofline']['frac']))"
   done
 done
