@@ -1,4 +1,5 @@
-// Multi-head attention core for short sequences (Sk <= 320) on gfx950 MFMA.
+// Multi-head attention core on gfx950 MFMA: short sequences (Sk <= 320) below, the streaming kernels for longer ones further down
+// (attn_long_kernel, attn_kvl_kernel).
 //
 // Forward / dQ kernels: one workgroup (4 waves) per (batch, head, 64-query tile); each wave owns
 // 16 queries and holds the WHOLE score row block in registers (no online softmax needed: Sk <= 320).
@@ -1463,7 +1464,7 @@ int launch_kv2_c(AttnK p, hipStream_t st) {
 }
 template <int DHK, int DHV>
 int launch_kv2(AttnK p, hipStream_t st) {
-  if (p.Sq > 320) return -1;
+  if (p.Sq > 320) return -1;                        // (any Sk: the key tiles are a loop; the resident queries are what is bounded)
   p.sqp = ((p.Sq + 31) / 32) * 32;
   if (p.sqp <= 128) return p.causal ? launch_kv2_c<DHK, DHV, 8, true>(p, st) : launch_kv2_c<DHK, DHV, 8, false>(p, st);
   return p.causal ? launch_kv2_c<DHK, DHV, 20, true>(p, st) : launch_kv2_c<DHK, DHV, 20, false>(p, st);
@@ -1491,7 +1492,7 @@ int launch_bwd1_c(AttnK p, hipStream_t st) {
 }
 template <int DHK, int DHV>
 int launch_bwd1(AttnK p, hipStream_t st) {
-  if (p.Sq > 320) return -1;
+  if (p.Sq > 320 || p.skp > 320) return -1;        // (NKT = 20 holds 320 keys: longer rows are the streaming kernels')
   p.sqp = ((p.Sq + 31) / 32) * 32;
   const bool q8 = p.sqp <= 128, k8 = p.skp <= 128;
   if (p.causal) return (q8 && k8) ? launch_bwd1_c<DHK, DHV, 8, 8, true>(p, st) : -1;
@@ -1515,6 +1516,7 @@ int dispatch_bwd1(const AttnK& p, hipStream_t st) {
 
 template <typename T, int MODE>
 int dispatch_q(const AttnK& p, hipStream_t st) {
+  if (p.skp > 320) return (int)hipErrorInvalidValue;          // (NT = 20 holds 320 keys: longer rows are the streaming kernels')
   const bool small = p.skp <= 128;
 #define GO(DHK, DHV) return small ? launch_q<T, DHK, DHV, 8, MODE>(p, st) : launch_q<T, DHK, DHV, 20, MODE>(p, st)
   switch (p.dh) {
@@ -1550,13 +1552,613 @@ int dispatch_kv(const AttnK& p, hipStream_t st) {
   return (int)hipErrorInvalidValue;
 }
 
+// ================================================================================================================================
+// Long sequences: streaming kernels for every shape the kernels above cannot hold -- Sk > 320, and the precise-mode (fp32) shapes
+// whose K / V (dQ: + K^T) exceed the LDS.  Nothing above is changed by them: gpv_attention_fwd / _bwd send a shape here only where
+// the short kernel would refuse it (q_short_fits).  Their LDS depends on (dtype, dh) only, never on Sq or Sk.
+//
+// Forward / dQ (attn_long_kernel): one workgroup of 8 waves per (batch, head, 128 queries); a wave owns a 16-query tile whose Q (dQ:
+// + dO, delta, lse) fragments stay in registers, and the keys pass through LDS in tiles of KT = 16 NTT keys, double buffered: the
+// global loads of tile t + 1 are issued before tile t's products and stored behind them, one barrier per tile.  The score layout is
+// attn_q_kernel's swapped S^T = mfma(K, Q): a lane owns one query, so the online softmax's running max is a register reduction plus
+// the two xor-shuffles (16, 32), and the running sum stays a per-lane partial until the end.  Every tile rescales O and the sum by
+// exp(scale (m_old - m_new)) -- no deferred max: the factor is 1 when the max did not grow, 0 while no key was live.  lse = m scale +
+// log(sum), exactly what attn_q_kernel writes, so either backward reads either forward's lse.
+// dQ recomputes P = exp(S scale - lse) per key tile from the saved lse (no rescaling), dS = P (dP - delta) scale and accumulates
+// dQ^T += K^T dS^T in registers: no atomics, no workspace.  Scores are accumulated in the forward's order (precise: hi hi, lo hi,
+// hi lo), dropout words are attn_q_kernel's, indexed by the GLOBAL key tile.
+// Tile sizes: the largest KT in {128, 64, 32} whose two stages fit 80 KB (two workgroups per CU).
+template <typename T, int DHK, int DHV, int MODE> struct LongQ {
+  static constexpr int NS = sizeof(T) == 4 ? 2 : 1;
+  static constexpr int bytes(int ntt) {            // one stage: K[KT][KP] | X^T[DHV][KT + 8] | (dQ) V[KT][KP]  (x hi, lo) | kbias[KT]
+    return ((ntt * 16 * (DHK + 8)) * NS * (MODE ? 2 : 1) + DHV * (ntt * 16 + 8) * NS) * 2 + ntt * 16 * 4;
+  }
+  static constexpr int NTT = 2 * bytes(8) <= 80 * 1024 ? 8 : 2 * bytes(4) <= 80 * 1024 ? 4 : 2;
+  static constexpr int STAGE = bytes(NTT);
+};
+
+template <typename T, int DHK, int DHV, int MODE, bool MASKED>
+__global__ __launch_bounds__(QTHR) void attn_long_kernel(AttnK p) {
+  if (p.dthresh) p.seed = eff_seed(p.seed, p.seed_dev);
+  using C = LongQ<T, DHK, DHV, MODE>;
+  constexpr bool PRECISE = sizeof(T) == 4;
+  constexpr int NTT = C::NTT, KT = NTT * 16, KP = DHK + 8, KC = DHK / 32, DT = DHV / 16, VTP = KT + 8, NS = C::NS;
+  constexpr int RE = KT * KP, CE = DHV * VTP;      // bf16 elements of a row-major / transposed tile image
+  constexpr int OKL = RE, OT = RE * NS, OTL = OT + CE, OV = OT + CE * NS, OVL = OV + RE, OB = OV + (MODE ? RE * NS : 0);
+  constexpr int SE = C::STAGE / 2;                 // stage pitch in bf16 elements
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  bf16* sm = reinterpret_cast<bf16*>(smem_raw);
+
+  const int nqt = (p.Sq + 15) >> 4;
+  int b, h, xs;
+  {                                                // (XCD-contiguous (batch, head, query block) ranges, as in attn_q_kernel)
+    const int nsp = p.nsplit, total = (int)gridDim.x;
+    const int qd = total >> 3, r = total & 7, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
+    const int v = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + loc;
+    xs = v % nsp;
+    const int bh = v / nsp;
+    h = bh % p.H; b = bh / p.H;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const int qt = xs * QW + wave;
+  const bool live = qt < nqt;                      // (wave-uniform: a wave past the last query tile only stages)
+  const int q = qt * 16 + (lane & 15);
+  const bool qok = q < p.Sq;
+  const int qc = min(q, p.Sq - 1);
+
+  // this lane's query fragments (unconditional loads: rows beyond Sq re-read the last one and are never stored)
+  bf16x8 qh[KC], ql[KC], doh[KC], dol[KC];
+  float delta = 0.f, lse0 = 0.f;
+  {
+    const T* qp = reinterpret_cast<const T*>(p.q) + b * p.q_bs + (int64_t)qc * p.q_rs + h * p.dh;
+    const T* dop = reinterpret_cast<const T*>(p.dout) + b * p.do_bs + (int64_t)qc * p.do_rs + h * p.dh;
+    const T* op = reinterpret_cast<const T*>(p.o) + b * p.o_bs + (int64_t)qc * p.o_rs + h * p.dh;
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) {
+      const bool dpad = kc * 32 + g * 8 >= p.dh;
+      const int d0 = min(kc * 32 + g * 8, p.dh - 8);
+      R8<T> x;
+      x.load(qp + d0);
+      if (dpad) x.zero();
+      qh[kc] = x.hi(); ql[kc] = x.lo();
+      if constexpr (MODE == 1) {
+        R8<T> y, z;
+        y.load(dop + d0); z.load(op + d0);
+        if (dpad) { y.zero(); z.zero(); }
+        doh[kc] = y.hi(); dol[kc] = y.lo();
+#pragma unroll
+        for (int e = 0; e < 8; ++e) delta += y.v[e] * z.v[e];
+      }
+    }
+    if constexpr (MODE == 1) {
+      delta += __shfl_xor(delta, 16); delta += __shfl_xor(delta, 32);
+      lse0 = p.lse[((int64_t)b * p.H + h) * p.Sq + qc];
+    }
+  }
+
+  // key tiles: causal rows end at their query, so a block stops after the tile of its last query
+  int nkt = (p.Sk + KT - 1) / KT;
+  if (MASKED && p.causal) nkt = min(nkt, (min(p.Sq, (xs + 1) * QW * 16) - 1) / KT + 1);
+  const T* kg = reinterpret_cast<const T*>(p.k) + b * p.k_bs + h * p.dh;
+  const T* vg = reinterpret_cast<const T*>(p.v) + b * p.v_bs + h * p.dh;
+  RowBatch<T, DHK, KT, QTHR> kr, vr;
+  ColBatch<T, DHV, KT, QTHR> xc;
+  float nb = 0.f;
+  auto load = [&](int t) {
+    const int k0 = t * KT, kv = min(KT, p.Sk - k0);
+    kr.load(kg + (int64_t)k0 * p.k_rs, p.k_rs, kv, KT, p.dh);
+    if constexpr (MODE == 0) {
+      xc.load(vg + (int64_t)k0 * p.v_rs, p.v_rs, kv, KT);
+    } else {
+      xc.load(kg + (int64_t)k0 * p.k_rs, p.k_rs, kv, KT);
+      vr.load(vg + (int64_t)k0 * p.v_rs, p.v_rs, kv, KT, p.dh);
+    }
+    const int key = k0 + (int)threadIdx.x;
+    if (threadIdx.x < KT) nb = (key >= p.Sk || (p.kpm && p.kpm[(int64_t)b * p.Sk + key])) ? -INFINITY : 0.f;
+  };
+  auto store = [&](int s) {
+    bf16* base = sm + s * SE;
+    kr.template store<PRECISE>(KT, base, base + OKL);
+    xc.template store<PRECISE>(KT, VTP, base + OT, base + OTL);
+    if constexpr (MODE == 1) vr.template store<PRECISE>(KT, base + OV, base + OVL);
+    if (threadIdx.x < KT) reinterpret_cast<float*>(base + OB)[threadIdx.x] = nb;
+  };
+
+  const float c2 = p.scale * 1.4426950408889634f;
+  const uint32_t rs0 = p.dthresh ? attn_row_seed(p.seed, ((uint64_t)b * p.H + h) * p.Sq + q) : 0u;
+  const uint32_t gb = rs0 + (uint32_t)(g * 2) * ATTN_PAIR_STEP;
+  const int ts = attn_ts(p.dthresh);
+  const uint32_t ts2 = ((uint32_t)ts & 0xffffu) * 0x10001u;
+  const float lse1 = lse0 > -INFINITY ? -lse0 * 1.4426950408889634f : 0.f;   // (dQ) exp(s scale - lse) = exp2(s c2 + lse1)
+  float m = -INFINITY, l = 0.f;                    // (forward) running max (raw score units) and this lane's partial sum
+  f32x4 acc[DT];                                   // O^T (forward) or dQ^T (dQ): lane = query, d = dt * 16 + g * 4 + i
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (nkt > 0) { load(0); store(0); }
+  __syncthreads();
+  for (int t = 0; t < nkt; ++t) {
+    load(min(t + 1, nkt - 1));                     // (unconditional: the last iteration re-reads its own tile, never stored)
+    const bf16* base = sm + (t & 1) * SE;
+    const bf16* Kh = base;
+    const bf16* Kl = base + OKL;
+    const bf16* Th = base + OT;
+    const bf16* Tl = base + OTL;
+    const float* kbias = reinterpret_cast<const float*>(base + OB);
+    const int k0 = t * KT;
+    if (live) {
+      if constexpr (MODE == 0) {
+        f32x4 s[NTT];
+#pragma unroll
+        for (int j = 0; j < NTT; ++j) {
+          s[j] = *reinterpret_cast<const f32x4*>(kbias + j * 16 + g * 4);
+#pragma unroll
+          for (int kc = 0; kc < KC; ++kc) {
+            const int off = (j * 16 + (lane & 15)) * KP + kc * 32 + g * 8;
+            const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Kh + off);
+            s[j] = mfma16(kh, qh[kc], s[j]);
+            if (PRECISE) {
+              const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Kl + off);
+              s[j] = mfma16(kl, qh[kc], s[j]);
+              s[j] = mfma16(kh, ql[kc], s[j]);
+            }
+          }
+        }
+        if constexpr (MASKED) {
+          if (p.causal) {
+#pragma unroll
+            for (int j = 0; j < NTT; ++j)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) s[j][i] = (k0 + j * 16 + g * 4 + i > q) ? -INFINITY : s[j][i];
+          }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < NTT; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[j][i]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float mn = fmaxf(m, mx);
+        const float nm = mn == -INFINITY ? 0.f : -mn * c2;
+        const float al = __builtin_amdgcn_exp2f(fmaf(m, c2, nm));     // exp(scale (m_old - m_new)): 0 while m_old = -inf
+        m = mn;
+        l *= al;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) acc[dt] *= al;
+#pragma unroll
+        for (int j = 0; j < NTT; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { const float e = __builtin_amdgcn_exp2f(fmaf(s[j][i], c2, nm)); s[j][i] = e; l += e; }
+        if (PRECISE && p.dthresh) {
+#pragma unroll
+          for (int j = 0; j < NTT; ++j) {
+            const uint32_t J = (uint32_t)(t * NTT + j);
+            const uint32_t w0 = attn_pair_bits(gb + J * 8 * ATTN_PAIR_STEP);
+            const uint32_t w1 = attn_pair_bits(gb + (J * 8 + 1) * ATTN_PAIR_STEP);
+            s[j][0] = attn_keep_lo(w0, ts) ? s[j][0] : 0.f;
+            s[j][1] = attn_keep_hi(w0, ts) ? s[j][1] : 0.f;
+            s[j][2] = attn_keep_lo(w1, ts) ? s[j][2] : 0.f;
+            s[j][3] = attn_keep_hi(w1, ts) ? s[j][3] : 0.f;
+          }
+        }
+#pragma unroll
+        for (int kb = 0; kb < NTT / 2; ++kb) {
+          bf16x8 ph, pl;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float a = s[2 * kb][i], c = s[2 * kb + 1][i];
+            ph[i] = (bf16)a; ph[4 + i] = (bf16)c;
+            if (PRECISE) { pl[i] = (bf16)(a - (float)ph[i]); pl[4 + i] = (bf16)(c - (float)ph[4 + i]); }
+          }
+          if (!PRECISE && p.dthresh) {
+            u32x4 pw = __builtin_bit_cast(u32x4, ph);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              const uint32_t pb = gb + (uint32_t)((t * NTT + 2 * kb + u) * 8) * ATTN_PAIR_STEP;
+              pw[2 * u] &= ~attn_drop_bits(attn_pair_bits(pb), ts2);
+              pw[2 * u + 1] &= ~attn_drop_bits(attn_pair_bits(pb + ATTN_PAIR_STEP), ts2);
+            }
+            ph = __builtin_bit_cast(bf16x8, pw);
+          }
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt) {
+            const int off = (dt * 16 + (lane & 15)) * VTP + kb * 32 + g * 4;
+            const bf16x8 xh = ld_pair64(Th + off, Th + off + 16);
+            acc[dt] = mfma16(xh, ph, acc[dt]);
+            if (PRECISE) {
+              const bf16x8 xl = ld_pair64(Tl + off, Tl + off + 16);
+              acc[dt] = mfma16(xl, ph, acc[dt]);
+              acc[dt] = mfma16(xh, pl, acc[dt]);
+            }
+          }
+        }
+      } else {
+        const bf16* Vh = base + OV;
+        const bf16* Vl = base + OVL;
+#pragma unroll
+        for (int kb = 0; kb < NTT / 2; ++kb) {
+          f32x4 sj[2];
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            const int j = 2 * kb + u;
+            f32x4 sc = *reinterpret_cast<const f32x4*>(kbias + j * 16 + g * 4), dp = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kc = 0; kc < KC; ++kc) {
+              const int off = (j * 16 + (lane & 15)) * KP + kc * 32 + g * 8;
+              const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Kh + off);
+              const bf16x8 vh = *reinterpret_cast<const bf16x8*>(Vh + off);
+              sc = mfma16(kh, qh[kc], sc);
+              dp = mfma16(vh, doh[kc], dp);
+              if (PRECISE) {
+                const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Kl + off);
+                const bf16x8 vl = *reinterpret_cast<const bf16x8*>(Vl + off);
+                sc = mfma16(kl, qh[kc], sc);
+                sc = mfma16(kh, ql[kc], sc);
+                dp = mfma16(vl, doh[kc], dp);
+                dp = mfma16(vh, dol[kc], dp);
+              }
+            }
+            uint32_t w01 = 0u, w23 = 0u;
+            if (p.dthresh) {
+              const uint32_t pb = rs0 + (uint32_t)((t * NTT + j) * 8 + g * 2) * ATTN_PAIR_STEP;
+              w01 = attn_pair_bits(pb); w23 = attn_pair_bits(pb + ATTN_PAIR_STEP);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int key = k0 + j * 16 + g * 4 + i;
+              float pr = __builtin_amdgcn_exp2f(fmaf(sc[i], c2, lse1));        // normalised P (0 for dead keys: sc = -inf)
+              if (MASKED && p.causal) pr = key > q ? 0.f : pr;
+              float d = dp[i];
+              if (p.dthresh) {
+                const uint32_t w = i < 2 ? w01 : w23;
+                d = ((i & 1) ? attn_keep_hi(w, ts) : attn_keep_lo(w, ts)) ? d * p.dscale : 0.f;
+              }
+              sj[u][i] = pr * (d - delta) * p.scale;
+            }
+          }
+          bf16x8 ph, pl;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float a = sj[0][i], c = sj[1][i];
+            ph[i] = (bf16)a; ph[4 + i] = (bf16)c;
+            pl[i] = (bf16)(a - (float)ph[i]); pl[4 + i] = (bf16)(c - (float)ph[4 + i]);
+          }
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt) {
+            const int off = (dt * 16 + (lane & 15)) * VTP + kb * 32 + g * 4;
+            const bf16x8 xh = ld_pair64(Th + off, Th + off + 16);
+            acc[dt] = mfma16(xh, ph, acc[dt]);
+            if (PRECISE) {
+              const bf16x8 xl = ld_pair64(Tl + off, Tl + off + 16);
+              acc[dt] = mfma16(xl, ph, acc[dt]);
+              acc[dt] = mfma16(xh, pl, acc[dt]);
+            }
+          }
+        }
+      }
+    }
+    if (t + 1 < nkt) store((t + 1) & 1);
+    __syncthreads();
+  }
+  if (!live) return;
+  float inv = 1.f;
+  if constexpr (MODE == 0) {
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    if (g == 0 && qok && p.lse) p.lse[((int64_t)b * p.H + h) * p.Sq + q] = (m == -INFINITY ? 0.f : m * p.scale) + logf(l);
+    inv = l > 0.f ? (p.dthresh ? p.dscale : 1.f) / l : 0.f;
+  }
+  if (!qok) return;
+  T* outp = MODE == 0 ? reinterpret_cast<T*>(p.o) + b * p.o_bs + (int64_t)q * p.o_rs + h * p.dh
+                      : reinterpret_cast<T*>(p.dq) + b * p.q_bs + (int64_t)q * p.q_rs + h * p.dh;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    const int d = dt * 16 + g * 4;
+    if (sizeof(T) == 4) {
+      *reinterpret_cast<float4*>(reinterpret_cast<float*>(outp) + d) =
+          make_float4(acc[dt][0] * inv, acc[dt][1] * inv, acc[dt][2] * inv, acc[dt][3] * inv);
+    } else {
+      bf16x4 o4;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o4[i] = (bf16)(acc[dt][i] * inv);
+      *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(outp) + d) = o4;
+    }
+  }
+}
+
+// dK / dV for long sequences (attn_kvl_kernel): one workgroup of 8 waves per (batch, head, 128 keys); a wave owns 16 keys, their K / V
+// fragments and dK / dV accumulators stay in registers, and the queries pass through LDS in chunks of QC, double buffered like
+// attn_long_kernel's key tiles: Q and dO row-major (score products) and transposed (dK / dV products), with every query's
+// -lse log2(e), delta = dO.O (QTHR / QC threads per query and an xor-shuffle sum) and dropout row seed.  The products and their
+// accumulation order are attn_kv_kernel's (precise mode: the recomputed scores equal the forward's bit for bit).
+// (attn_kv_kernel serves any length too, but re-stages each 64-query chunk per 64 keys behind two barriers with the loads of a
+//  chunk exposed, and sums delta serially in 64 threads: the long backward was about half as fast through it.)
+template <typename T, int DHK, int DHV> struct LongKV {
+  static constexpr int NS = sizeof(T) == 4 ? 2 : 1;
+  static constexpr int bytes(int qc) {             // one stage: Q, dO [QC][KP] | Q^T, dO^T [DHV][QC + 8]  (x hi, lo) | lse, delta, seed [QC]
+    return (2 * qc * (DHK + 8) * NS + 2 * DHV * (qc + 8) * NS) * 2 + 3 * qc * 4;
+  }
+  static constexpr int QC = 2 * bytes(64) <= 80 * 1024 ? 64 : 32;
+  static constexpr int STAGE = bytes(QC);
+};
+
+template <typename T, int DHK, int DHV>
+__global__ __launch_bounds__(QTHR) void attn_kvl_kernel(AttnK p) {
+  if (p.dthresh) p.seed = eff_seed(p.seed, p.seed_dev);
+  using C = LongKV<T, DHK, DHV>;
+  constexpr bool PRECISE = sizeof(T) == 4;
+  constexpr int QC = C::QC, KP = DHK + 8, KC = DHK / 32, DT = DHV / 16, QTP = QC + 8, NS = C::NS, DG = DHV / 8, TPQ = QTHR / QC, NDC = (DG + TPQ - 1) / TPQ;
+  constexpr int RE = QC * KP, CE = DHV * QTP;
+  constexpr int OQL = RE, OD = RE * NS, ODL = OD + RE, OQT = OD + RE * NS, OQTL = OQT + CE, ODT = OQT + CE * NS, ODTL = ODT + CE,
+                OF = ODT + CE * NS, SE = C::STAGE / 2;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  bf16* sm = reinterpret_cast<bf16*>(smem_raw);
+
+  int b, h, xs;
+  {
+    const int nsp = p.nsplit, total = (int)gridDim.x;
+    const int qd = total >> 3, r = total & 7, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
+    const int v = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + loc;
+    xs = v % nsp;
+    const int bh = v / nsp;
+    h = bh % p.H; b = bh / p.H;
+  }
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
+  const int k0 = xs * QW * 16;
+  const int key = k0 + wave * 16 + (lane & 15);
+  const bool kok = key < p.Sk;
+  const bool wlive = k0 + wave * 16 < p.Sk;        // (wave-uniform)
+  bool kdead = !kok;
+  if (kok && p.kpm) kdead = p.kpm[(int64_t)b * p.Sk + key] != 0;
+  const float c2k = p.scale * 1.4426950408889634f;
+  const uint32_t kpair = (uint32_t)(key >> 1) * ATTN_PAIR_STEP, kshift = (key & 1) * 16;
+  const int ts = attn_ts(p.dthresh);
+
+  bf16x8 kh[KC], kl[KC], vh[KC], vl[KC];
+  {
+    const T* kp_ = reinterpret_cast<const T*>(p.k) + b * p.k_bs + (int64_t)key * p.k_rs + h * p.dh;
+    const T* vp_ = reinterpret_cast<const T*>(p.v) + b * p.v_bs + (int64_t)key * p.v_rs + h * p.dh;
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) {
+      const int d0 = kc * 32 + g * 8;
+      R8<T> x, y;
+      if (kok && d0 < p.dh) { x.load(kp_ + d0); y.load(vp_ + d0); } else { x.zero(); y.zero(); }
+      kh[kc] = x.hi(); kl[kc] = x.lo(); vh[kc] = y.hi(); vl[kc] = y.lo();
+    }
+  }
+  f32x4 dkacc[DT], dvacc[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) { dkacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dvacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+  const T* qg = reinterpret_cast<const T*>(p.q) + b * p.q_bs + h * p.dh;
+  const T* dog = reinterpret_cast<const T*>(p.dout) + b * p.do_bs + h * p.dh;
+  const T* og = reinterpret_cast<const T*>(p.o) + b * p.o_bs + h * p.dh;
+  RowBatch<T, DHK, QC, QTHR> qr, dr;
+  ColBatch<T, DHV, QC, QTHR> qcb, dcb;
+  Raw8<T> ua[NDC], wa[NDC];                        // delta: query row tid / TPQ, column groups tid % TPQ + TPQ m
+  float nls = 0.f;
+  const int dr_ = tid / TPQ, dsub = tid % TPQ;
+  auto load = [&](int c) {
+    const int q0 = c * QC, nq = min(QC, p.Sq - q0);
+    qr.load(qg + (int64_t)q0 * p.q_rs, p.q_rs, nq, QC, p.dh);
+    dr.load(dog + (int64_t)q0 * p.do_rs, p.do_rs, nq, QC, p.dh);
+    qcb.load(qg + (int64_t)q0 * p.q_rs, p.q_rs, nq, QC);
+    dcb.load(dog + (int64_t)q0 * p.do_rs, p.do_rs, nq, QC);
+    const int rq = q0 + min(dr_, nq - 1);
+#pragma unroll
+    for (int mm = 0; mm < NDC; ++mm) {
+      const int cg = min(dsub + TPQ * mm, DG - 1);
+      ua[mm].load(dog + (int64_t)rq * p.do_rs + cg * 8);
+      wa[mm].load(og + (int64_t)rq * p.o_rs + cg * 8);
+    }
+    nls = p.lse[((int64_t)b * p.H + h) * p.Sq + rq];
+  };
+  auto store = [&](int c, int s) {
+    bf16* base = sm + s * SE;
+    qr.template store<PRECISE>(QC, base, base + OQL);
+    dr.template store<PRECISE>(QC, base + OD, base + ODL);
+    qcb.template store<PRECISE>(QC, QTP, base + OQT, base + OQTL);
+    dcb.template store<PRECISE>(QC, QTP, base + ODT, base + ODTL);
+    float dl = 0.f;
+#pragma unroll
+    for (int mm = 0; mm < NDC; ++mm) {
+      if (dsub + TPQ * mm < DG) {
+        const R8<T> u = ua[mm].get(), w = wa[mm].get();
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dl += u.v[e] * w.v[e];
+      }
+    }
+#pragma unroll
+    for (int x = 1; x < TPQ; x *= 2) dl += __shfl_xor(dl, x);
+    if (dsub == 0 && dr_ < QC) {
+      const int qq = c * QC + dr_;
+      const bool ok = qq < p.Sq;
+      float* lse_s = reinterpret_cast<float*>(base + OF);
+      lse_s[dr_] = ok ? -nls * 1.4426950408889634f : -INFINITY;          // padded queries: P = 0
+      lse_s[QC + dr_] = ok ? dl : 0.f;
+      reinterpret_cast<uint32_t*>(lse_s + 2 * QC)[dr_] = p.dthresh ? attn_row_seed(p.seed, ((uint64_t)b * p.H + h) * p.Sq + qq) : 0u;
+    }
+  };
+
+  // causal: queries before the block's first key see none of its keys
+  const int nc = (p.Sq + QC - 1) / QC;
+  const int cs = p.causal ? min(k0 / QC, nc) : 0;
+  if (cs < nc) { load(cs); store(cs, 0); }
+  __syncthreads();
+  for (int c = cs; c < nc; ++c) {
+    load(min(c + 1, nc - 1));                      // (unconditional: the last iteration re-reads its own chunk, never stored)
+    const bf16* base = sm + ((c - cs) & 1) * SE;
+    const bf16* Qh = base;
+    const bf16* Ql = base + OQL;
+    const bf16* Dh = base + OD;
+    const bf16* Dl = base + ODL;
+    const bf16* QTh = base + OQT;
+    const bf16* QTl = base + OQTL;
+    const bf16* DTh = base + ODT;
+    const bf16* DTl = base + ODTL;
+    const float* lse_s = reinterpret_cast<const float*>(base + OF);
+    const float* del_s = lse_s + QC;
+    const uint32_t* rs_s = reinterpret_cast<const uint32_t*>(lse_s + 2 * QC);
+    const int q0 = c * QC;
+    if (wlive) {
+#pragma unroll
+      for (int qb = 0; qb < QC / 32; ++qb) {
+        if (q0 + qb * 32 >= p.Sq) break;
+        f32x4 pr[2], ds[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          f32x4 sa = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kc = 0; kc < KC; ++kc) {
+            const int off = (qb * 32 + u * 16 + (lane & 15)) * KP + kc * 32 + g * 8;
+            const bf16x8 qh_ = *reinterpret_cast<const bf16x8*>(Qh + off);
+            const bf16x8 dh_ = *reinterpret_cast<const bf16x8*>(Dh + off);
+            sa = mfma16(qh_, kh[kc], sa);
+            dp = mfma16(dh_, vh[kc], dp);
+            if (PRECISE) {
+              const bf16x8 ql_ = *reinterpret_cast<const bf16x8*>(Ql + off);
+              const bf16x8 dl_ = *reinterpret_cast<const bf16x8*>(Dl + off);
+              sa = mfma16(qh_, kl[kc], sa); sa = mfma16(ql_, kh[kc], sa);
+              dp = mfma16(dh_, vl[kc], dp); dp = mfma16(dl_, vh[kc], dp);
+            }
+          }
+          const int qr_ = qb * 32 + u * 16 + g * 4;            // local query row of element i = qr_ + i
+          const float4 l4 = *reinterpret_cast<const float4*>(lse_s + qr_);
+          const float4 d4 = *reinterpret_cast<const float4*>(del_s + qr_);
+          const float ls[4] = {l4.x, l4.y, l4.z, l4.w};
+          const float dl[4] = {d4.x, d4.y, d4.z, d4.w};
+          uint32_t rsd[4] = {0u, 0u, 0u, 0u};
+          if (p.dthresh) {
+            const uint4 r4 = *reinterpret_cast<const uint4*>(rs_s + qr_);
+            rsd[0] = r4.x; rsd[1] = r4.y; rsd[2] = r4.z; rsd[3] = r4.w;
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const bool dead = kdead || (p.causal && key > q0 + qr_ + i);
+            float pv = __builtin_amdgcn_exp2f(fmaf(sa[i], c2k, ls[i]));
+            pv = dead ? 0.f : pv;
+            float d = dp[i], pd = pv;
+            if (p.dthresh) {
+              const uint32_t w = attn_pair_bits(rsd[i] + kpair);
+              const bool keep = (int)(short)((w >> kshift) & 0xffffu) >= ts;
+              d = keep ? d * p.dscale : 0.f;
+              pd = keep ? pv * p.dscale : 0.f;
+            }
+            pr[u][i] = pd;
+            ds[u][i] = pv * (d - dl[i]) * p.scale;
+          }
+        }
+        bf16x8 ph, pl, sh, sl;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          ph[i] = (bf16)pr[0][i]; ph[4 + i] = (bf16)pr[1][i];
+          pl[i] = (bf16)(pr[0][i] - (float)ph[i]); pl[4 + i] = (bf16)(pr[1][i] - (float)ph[4 + i]);
+          sh[i] = (bf16)ds[0][i]; sh[4 + i] = (bf16)ds[1][i];
+          sl[i] = (bf16)(ds[0][i] - (float)sh[i]); sl[4 + i] = (bf16)(ds[1][i] - (float)sh[4 + i]);
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+          const int off = (dt * 16 + (lane & 15)) * QTP + qb * 32 + g * 4;
+          const bf16x8 dth = ld_pair64(DTh + off, DTh + off + 16);
+          const bf16x8 qth = ld_pair64(QTh + off, QTh + off + 16);
+          dvacc[dt] = mfma16(dth, ph, dvacc[dt]);
+          dkacc[dt] = mfma16(qth, sh, dkacc[dt]);
+          if (PRECISE) {
+            const bf16x8 dtl = ld_pair64(DTl + off, DTl + off + 16);
+            const bf16x8 qtl = ld_pair64(QTl + off, QTl + off + 16);
+            dvacc[dt] = mfma16(dtl, ph, dvacc[dt]); dvacc[dt] = mfma16(dth, pl, dvacc[dt]);
+            dkacc[dt] = mfma16(qtl, sh, dkacc[dt]); dkacc[dt] = mfma16(qth, sl, dkacc[dt]);
+          }
+        }
+      }
+    }
+    if (c + 1 < nc) store(c + 1, (c + 1 - cs) & 1);
+    __syncthreads();
+  }
+  if (!kok) return;
+  T* dkp = reinterpret_cast<T*>(p.dk) + b * p.k_bs + (int64_t)key * p.k_rs + h * p.dh;
+  T* dvp = reinterpret_cast<T*>(p.dv) + b * p.v_bs + (int64_t)key * p.v_rs + h * p.dh;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    const int d = dt * 16 + g * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { dkp[d + i] = (T)dkacc[dt][i]; dvp[d + i] = (T)dvacc[dt][i]; }
+  }
+}
+
+template <typename T, int DHK, int DHV, int MODE, bool MASKED>
+int launch_long_f(AttnK p, hipStream_t st) {
+  constexpr size_t lds = 2 * (size_t)LongQ<T, DHK, DHV, MODE>::STAGE;
+  static_assert(lds <= 160 * 1024, "attn_long_kernel: two stages exceed the LDS");
+  auto fn = attn_long_kernel<T, DHK, DHV, MODE, MASKED>;
+  static bool attr = false;
+  if (lds > 64 * 1024 && !attr) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+    attr = true;
+  }
+  p.nsplit = ((p.Sq + 15) / 16 + QW - 1) / QW;     // query blocks of 8 tiles per (batch, head)
+  hipLaunchKernelGGL(fn, dim3(p.nsplit * p.B * p.H), dim3(QTHR), lds, st, p);
+  GPV_CHECK_LAUNCH();
+  return 0;
+}
+template <typename T, int MODE>
+int dispatch_long(const AttnK& p, hipStream_t st) {
+#define GO(DHK, DHV) return p.causal ? launch_long_f<T, DHK, DHV, MODE, true>(p, st) : launch_long_f<T, DHK, DHV, MODE, false>(p, st)
+  switch (p.dh) {
+    case 32: GO(32, 32);
+    case 48: GO(64, 48);
+    case 64: GO(64, 64);
+    case 96: GO(96, 96);
+  }
+#undef GO
+  return (int)hipErrorInvalidValue;
+}
+template <typename T, int DHK, int DHV>
+int launch_kvl(AttnK p, hipStream_t st) {
+  constexpr size_t lds = 2 * (size_t)LongKV<T, DHK, DHV>::STAGE;
+  static_assert(lds <= 160 * 1024, "attn_kvl_kernel: two stages exceed the LDS");
+  auto fn = attn_kvl_kernel<T, DHK, DHV>;
+  static bool attr = false;
+  if (lds > 64 * 1024 && !attr) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+    attr = true;
+  }
+  p.nsplit = (p.Sk + QW * 16 - 1) / (QW * 16);     // key blocks of 128 per (batch, head)
+  hipLaunchKernelGGL(fn, dim3(p.nsplit * p.B * p.H), dim3(QTHR), lds, st, p);
+  GPV_CHECK_LAUNCH();
+  return 0;
+}
+template <typename T>
+int dispatch_kvl(const AttnK& p, hipStream_t st) {
+  switch (p.dh) {
+    case 32: return launch_kvl<T, 32, 32>(p, st);
+    case 48: return launch_kvl<T, 64, 48>(p, st);
+    case 64: return launch_kvl<T, 64, 64>(p, st);
+    case 96: return launch_kvl<T, 96, 96>(p, st);
+  }
+  return (int)hipErrorInvalidValue;
+}
+
+// Does attn_q_kernel (MODE 0 forward, 1 dQ) serve this shape?  Sk <= 320 and its whole-row K / V (dQ: + K^T) within the LDS:
+// launch_q_f's own budget.  Every other shape goes to the streaming kernels above.
+template <typename T, int MODE>
+bool q_short_fits(const AttnK& p) {
+  if (p.Sk > 320) return false;
+  const size_t dhk = p.dh == 32 ? 32 : p.dh == 96 ? 96 : 64, kp = dhk + 8, vtp = (size_t)p.skp + 8;
+  const size_t elems = (size_t)p.skp * kp + (size_t)p.dh * vtp + (MODE ? (size_t)p.skp * kp : 0);
+  return elems * 2 * (sizeof(T) == 4 ? 2 : 1) + (size_t)p.skp * sizeof(float) <= 160 * 1024;
+}
+
 int fill(const gpv_attn_args* a, AttnK& p) {
-  if (!a || !a->q || !a->k || !a->v || a->Sk <= 0 || a->Sq <= 0 || a->Sk > 320) return (int)hipErrorInvalidValue;
+  if (!a || !a->q || !a->k || !a->v || a->Sk <= 0 || a->Sq <= 0) return (int)hipErrorInvalidValue;
   p.q = a->q; p.k = a->k; p.v = a->v; p.o = a->o;
   p.q_bs = a->q_bs; p.q_rs = a->q_rs; p.k_bs = a->k_bs; p.k_rs = a->k_rs; p.v_bs = a->v_bs; p.v_rs = a->v_rs;
   p.o_bs = a->o_bs; p.o_rs = a->o_rs;
   p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Sk = a->Sk; p.dh = a->dh;
-  p.skp = ((a->Sk + 63) / 64) * 64;      // key tiles come in groups of four (one uniform test per group in the kernels)
+  p.skp = ((a->Sk + 63) / 64) * 64;      // key tiles come in groups of four (one uniform test per group in the short kernels)
   p.scale = a->scale; p.kpm = a->kpm; p.causal = a->causal;
   p.dthresh = a->drop_p > 0.f ? drop_thresh(a->drop_p) : 0u;
   p.dscale = a->drop_p > 0.f ? 1.f / (1.f - a->drop_p) : 1.f;
@@ -1577,7 +2179,8 @@ extern "C" int gpv_attention_fwd(const gpv_attn_args* a, void* stream) {
   if (e) return e;
   if (!a->o) return (int)hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return a->dtype == GPV_F32 ? dispatch_q<float, 0>(p, st) : dispatch_q<bf16, 0>(p, st);
+  if (a->dtype == GPV_F32) return q_short_fits<float, 0>(p) ? dispatch_q<float, 0>(p, st) : dispatch_long<float, 0>(p, st);
+  return q_short_fits<bf16, 0>(p) ? dispatch_q<bf16, 0>(p, st) : dispatch_long<bf16, 0>(p, st);
 }
 
 template <int NT, bool FULL>
@@ -1604,7 +2207,8 @@ extern "C" int gpv_attention_qkv_fwd(const gpv_attn_args* a, const void* xp, con
   AttnK p{};
   int e = fill(a, p);
   if (e) return e;
-  if (!a->o || !xp || !x || !w || a->dtype != GPV_BF16 || a->dh != 32 || a->H * a->dh != 256 || a->Sq != a->Sk || a->causal) return (int)hipErrorInvalidValue;
+  if (!a->o || !xp || !x || !w || a->dtype != GPV_BF16 || a->dh != 32 || a->H * a->dh != 256 || a->Sq != a->Sk || a->Sk > 320 || a->causal)
+    return (int)hipErrorInvalidValue;
   if ((x_rs & 7) || (x_bs & 7) || (a->q_rs & 3) || (a->k_rs & 3) || (a->o_rs & 3)) return (int)hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(xp) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) & 15) return (int)hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->o)) & 7) return (int)hipErrorInvalidValue;
@@ -1624,6 +2228,12 @@ extern "C" int gpv_attention_bwd(const gpv_attn_args* a, void* stream) {
   if (e) return e;
   if (!a->o || !a->dout || !a->dq || !a->dk || !a->dv || !a->lse) return (int)hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool f32 = a->dtype == GPV_F32;
+  if (!(f32 ? q_short_fits<float, 1>(p) : q_short_fits<bf16, 1>(p))) {       // beyond the short kernels: dQ, then dK / dV, streamed
+    e = f32 ? dispatch_long<float, 1>(p, st) : dispatch_long<bf16, 1>(p, st);
+    if (e) return e;
+    return f32 ? dispatch_kvl<float>(p, st) : dispatch_kvl<bf16>(p, st);
+  }
   if (a->dtype != GPV_F32) {
     e = dispatch_bwd1(p, st);
     if (e >= 0) return e;

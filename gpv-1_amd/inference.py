@@ -114,7 +114,9 @@ def decode_outputs(outputs, model, num_output_boxes=None):
 @torch.no_grad()
 def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=None):
     """images: list of arrays/tensors (see preprocess_image); queries: list[str] or (ids, mask) tensors;
-    size: (H, W) to resize HxWx3 arrays to first (the data loader's 480x640), None = as they are (inference.py)"""
+    size: (H, W) to resize HxWx3 arrays to first (the data loader's 480x640), None = as they are (inference.py).  Any image size
+    runs: the batch is padded to its largest image and the encoder attends over ceil(H / 32) ceil(W / 32) tokens (850 for
+    800x1088), beyond 320 of them on the streaming attention kernels"""
     dev = model.vision_token.device
     if size is not None:
         images = [resize_image(i, size) if not torch.is_tensor(i) else i for i in images]
