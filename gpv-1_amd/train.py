@@ -186,6 +186,7 @@ class GraphedBody:
             RT.multi_wait = None
             self.chains, _ops.GradChain._live = _ops.GradChain._live, live_before
         self.fwd_touched = trainer.touched.clone()            # (forward kernels never write gradients: stays empty)
+        trainer._captures += 1
         trainer.touched |= saved
 
     def _abort_open(self):
@@ -550,6 +551,7 @@ class GraphedBody:
             RT.branch_stream = None
         RT.backward_milestone = milestone
         _trace('capture backward end: %d stage graphs' % len(b2_list))
+        tr._captures += 1
         var = {'head_late': head_late, 'b1': b1, 'b2': b2_list, 'grads': grads, 's_ce': s_ce, 'loss': loss_static, 'touched': tr.touched.clone(), 'dc5': dc5, 'deferred': deferred + side_a}
         tr.touched |= saved
         return var
@@ -571,6 +573,12 @@ class FlatTrainer:
         """what turns G / p.grad (sums over ranks after the exchange) into the reference's averaged gradients"""
         return self.avg
 
+    @property
+    def capture_count(self):
+        """graph captures finished so far (a body's forward pair counts once, every backward variant once): steady state and an
+        evaluation between two steps leave it where it is -- replays only"""
+        return self._captures
+
     def grad_norm(self, start=0, end=None):
         """L2 norm of the AVERAGED gradient over the flat range [start, end) -- what the reference would log from p.grad"""
         return self.G[start:self.total if end is None else end].norm() * self.grad_scale
@@ -591,6 +599,7 @@ class FlatTrainer:
         self._bodies, self._seen, self.stream = collections.OrderedDict(), {}, None      # captured bodies, least recently used first
         self.graph_slots = int(os.environ.get('GPV_TRAIN_GRAPH_SLOTS', '8'))             # each body pins its activation pool (a few GB at B = 32)
         self.graph_steps, self.eager_steps = 0, 0
+        self._captures = 0               # finished captures: one per GraphedBody forward, one per backward variant (capture_count)
         self._extra_cache = {}
         self.defer_wgrad = None          # decided below (single rank only): model-body weight gradients as a branch of the backbone backward graph
         # Python's cyclic collector costs 1-3 ms per step once it has a few hundred thousand module / tensor objects to

@@ -14,10 +14,22 @@ What is reproduced -- everything between the data loader and the checkpoint file
   * checkpoints in the reference layout (:381-389): ``model`` with ``module.``-prefixed keys (what a DDP-wrapped model
     saves and ``inference.py:59-60`` strips), ``optimizer``, ``epoch``, ``step``, ``lr``, ``model_selection_metric``,
     ``warmup_scheduler``; resume takes every key whose name and size match (:264-271).
-Out of scope (SURVEY §2): dataset ETL, evaluators (the reference checkpoints only when its validation metric improves;
-without evaluators this driver checkpoints every ``training.ckpt_step`` steps and at every epoch end), TensorBoard, HTML.
+  * train-time evaluation and model selection (:325-395) when the caller passes ``eval_datasets``: at the start of every
+    epoch (at launch only with ``training.run_eval_at_launch``) rank 0 evaluates every named dataset on the ``train`` and
+    ``val`` subsets with gpv1_amd.metrics (at most ``training.num_val_samples[name]`` samples each), logs the figures, forms
+    ``model_selection_metric = vqa_acc + cider + det_map + cls_acc`` on ``val`` and writes ``ckpt_dir/model.pth`` only when it
+    exceeds the best so far; the periodic and epoch-end saves go to ``model_last.pth`` (carrying the best metric so far), a
+    resume takes ``best_metric`` from the checkpoint (:283); the other ranks wait at a barrier.  Detection mAP is scored on
+    the device (csrc/det_ap.hip).  ``cider`` is 0 unless the dataset carries a caption ``scorer`` (Bleu / CIDEr are
+    un-vendored); the reference leaves ``refcocop`` out of the sum, so its mAP is logged only.  Evaluation leaves the
+    training state alone: ``model.eval()`` / ``no_grad`` / ``model.train()``, no RNG draw, the captured training graphs are
+    replayed afterwards, not recaptured.
+Out of scope: dataset ETL, TensorBoard, HTML.  Without ``eval_datasets`` this driver checkpoints every
+``training.ckpt_step`` steps and at every epoch end into ``model.pth``.
 The dataset is any sequence of ``(image[3,H,W] fp32 normalised, query str | (ids, mask), target dict)``;
-``SyntheticCocoDataset`` provides BASELINE's synthetic COCO-shaped samples.
+``SyntheticCocoDataset`` provides BASELINE's synthetic COCO-shaped samples.  An evaluation dataset is such a sequence with
+a ``samples`` list beside it (the reference's ``dataset.samples``: the dicts the evaluators read), optionally ``synonyms``
+(classification) and ``scorer`` (captioning).
 """
 import argparse
 import os
@@ -92,6 +104,88 @@ def batches(dataset, indices, batch_size, device):
         yield nested_tensor_from_tensor_list(imgs), queries, targets
 
 
+def eval_batches(dataset, batch_size, device):
+    """the evaluation loader (train_distr.py:336-341: shuffle=False, the last batch may be short)"""
+    n = len(dataset)
+    for s in range(0, n, batch_size):
+        items = [dataset[i] for i in range(s, min(n, s + batch_size))]
+        qs = [it[1] for it in items]
+        queries = qs if isinstance(qs[0], str) else (torch.stack([q[0] for q in qs]).to(device), torch.stack([q[1] for q in qs]).to(device))
+        yield nested_tensor_from_tensor_list([it[0].to(device) for it in items]), queries, [it[2] for it in items]
+
+
+def _eval_vqa(model, batches_, ds, limit):
+    from . import metrics
+    return metrics.vqa_accuracy(model, batches_, ds.samples, limit)
+
+
+def _eval_cls(model, batches_, ds, limit):
+    from . import metrics
+    return metrics.cls_metrics(model, batches_, ds.samples, limit, synonyms=getattr(ds, 'synonyms', None))
+
+
+def _eval_cap(model, batches_, ds, limit):
+    from . import metrics
+    scores, _ = metrics.cap_metrics(model, batches_, ds.samples, limit, scorer=getattr(ds, 'scorer', None))
+    return scores
+
+
+def _eval_det(model, batches_, ds, limit):
+    from . import metrics
+    return metrics.det_metrics(model, batches_, ds.samples, limit)
+
+
+def _eval_refexp(model, batches_, ds, limit):
+    from . import metrics
+    return metrics.refexp_metrics(model, batches_, ds.samples, limit)
+
+
+# dataset name -> (model, batches, dataset, limit) -> figure; the names of configs/learning_datasets/*.yaml
+EVAL_FNS = {'coco_vqa': _eval_vqa, 'coco_cls': _eval_cls, 'coco_cap': _eval_cap, 'coco_det': _eval_det, 'refcocop': _eval_refexp}
+
+
+def evaluate_subset(model, datasets, subset, cfg, epoch, device, log=print, said=None):
+    """train_distr.py:328-380 for one subset: every named dataset through its metric function, figures logged;
+    -> vqa_acc + cider + det_map + cls_acc (what is absent counts 0).  Leaves the model in the mode it was in and draws no random number.
+    said: a set that remembers the notes already logged (the missing caption scorer is mentioned once per run)."""
+    said = set() if said is None else said
+    tr_cfg = cfg.training
+    limits = tr_cfg.get('num_val_samples', None) or {}
+    batch_size = int(cfg.get('batch_size', None) or tr_cfg.batch_size)
+    vqa_acc = cls_acc = cider = det_map = 0
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for name, ds in datasets.items():
+                fn = EVAL_FNS.get(name)
+                if fn is None:
+                    log(f'Eval not implemented for {name}')
+                    continue
+                out = fn(model, eval_batches(ds, batch_size, device), ds, limits.get(name, None))
+                if name == 'coco_vqa':
+                    vqa_acc = out
+                    log(f'Dataset: {name} | Subset: {subset} | Epoch: {epoch} | Acc: {out}')
+                elif name == 'coco_cls':
+                    cls_acc = out
+                    log(f'Dataset: {name} | Subset: {subset} | Epoch: {epoch} | Acc: {out}')
+                elif name == 'coco_cap':
+                    if 'Cider' in out:
+                        cider = out['Cider']
+                        log(f"Dataset: {name} | Subset: {subset} | Epoch: {epoch} | Bleu1: {out.get('Bleu1')} | Bleu4: {out.get('Bleu4')} | Cider: {cider}")
+                    elif 'no_cider' not in said:
+                        said.add('no_cider')
+                        log(f'Dataset: {name}: no caption scorer was supplied (Bleu / CIDEr are not vendored): cider = 0 enters model_selection_metric')
+                elif name == 'coco_det':
+                    det_map = out
+                    log(f'Dataset: {name} | Subset: {subset} | Epoch: {epoch} | mAP: {out}')
+                else:
+                    log(f'Dataset: {name} | Subset: {subset} | Epoch: {epoch} | mAP: {out} (not part of model_selection_metric)')
+    finally:
+        model.train(was_training)
+    return vqa_acc + cider + det_map + cls_acc
+
+
 def save_checkpoint(path, model, trainer, epoch, step, metric=0.0):
     """train_distr.py:381-389 (DDP state dict => 'module.' prefix)"""
     sd = {'module.' + k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
@@ -118,8 +212,10 @@ def load_checkpoint(path, model, trainer=None, map_location='cpu'):
     return ckpt, taken
 
 
-def train_worker(cfg, dataset=None, device=None, log=print):
-    """one rank of the reference's ``train_worker``; returns (model, trainer, step)"""
+def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
+    """one rank of the reference's ``train_worker``; returns (model, trainer, step).
+    eval_datasets: None, or {'train' | 'val': {'coco_vqa' | 'coco_cls' | 'coco_cap' | 'coco_det' | 'refcocop': dataset}} -- evaluation
+    at every epoch start and best-metric checkpoints (module docstring)"""
     rank = int(os.environ.get('RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
     local = int(os.environ.get('LOCAL_RANK', 0))
@@ -165,17 +261,39 @@ def train_worker(cfg, dataset=None, device=None, log=print):
     trainer = FlatTrainer(model, lr=tr_cfg.lr, lr_backbone=tr_cfg.lr_backbone, weight_decay=tr_cfg.weight_decay,
                           clip_max_norm=tr_cfg.clip_max_norm,
                           warmup_steps=int(tr_cfg.lr_warmup_fraction * t_total) if tr_cfg.lr_warmup else 0, t_total=t_total, **sched)
-    step, last_epoch = 0, -1
+    step, last_epoch, best_metric, said = 0, -1, 0.0, set()
     if have_ckpt:
         ckpt, taken = load_checkpoint(tr_cfg.ckpt, model, trainer, map_location=device)
         step, last_epoch = ckpt['step'], ckpt['epoch']
+        if eval_datasets is not None:
+            best_metric = ckpt.get('model_selection_metric', 0.0) or 0.0   # a checkpoint is the best so far (train_distr.py:283)
         log(f'[rank {rank}] resumed {tr_cfg.ckpt}: {taken} tensors, end of epoch {last_epoch}, step {step}')
-    ckpt_path = os.path.join(cfg.ckpt_dir, 'model.pth')
+    best_path = os.path.join(cfg.ckpt_dir, 'model.pth')
+    # with evaluators model.pth is the best model so far and the running state goes next to it
+    ckpt_path = os.path.join(cfg.ckpt_dir, 'model_last.pth') if eval_datasets is not None else best_path
     if rank == 0:
         os.makedirs(cfg.ckpt_dir, exist_ok=True)
     max_steps = cfg.get('max_steps', None)
     t0 = time.time()
+    launch = True
     for epoch in range(last_epoch + 1, epochs):
+        if eval_datasets is not None and ((not launch) or tr_cfg.get('run_eval_at_launch', True)):
+            if rank == 0:
+                for subset in ('train', 'val'):
+                    if subset not in eval_datasets:
+                        continue
+                    metric = evaluate_subset(model, eval_datasets[subset], subset, cfg, epoch, device, log, said)
+                    if subset == 'val':
+                        log(f'Epoch: {epoch} | model_selection_metric: {metric} | best so far: {best_metric}')
+                        if metric > best_metric:
+                            log('Saving checkpoint ...')
+                            best_metric = metric
+                            save_checkpoint(best_path, model, trainer, epoch - 1, step, metric)
+            if world > 1:
+                dist.barrier()                                   # the other ranks wait for rank 0's evaluation
+                from .misc import note_sync_collective
+                note_sync_collective()
+        launch = False
         idx = shard_indices(len(dataset), epoch, rank, world)
         epoch_done = True                     # False: max_steps ended the epoch before its last batch
         batch_iter = iter(batches(dataset, idx, per_rank, device))
@@ -190,13 +308,13 @@ def train_worker(cfg, dataset=None, device=None, log=print):
                 # like the reference's mid-epoch save (train_distr.py:372-389: 'epoch': epoch-1 next to the CURRENT step): a
                 # resume re-runs this epoch from its start while the schedule continues from `step` -- the reference's behaviour,
                 # kept as is (with lr_linear_decay the tail of such a run sits at lr 0 once step passes t_total)
-                save_checkpoint(ckpt_path, model, trainer, epoch - 1, step)
+                save_checkpoint(ckpt_path, model, trainer, epoch - 1, step, best_metric)
             if max_steps is not None and step >= max_steps:
                 epoch_done = next(batch_iter, None) is None      # stopped on the epoch's last batch: the epoch is complete
                 break
         stopped = max_steps is not None and step >= max_steps
         if rank == 0:
-            save_checkpoint(ckpt_path, model, trainer, epoch if epoch_done else epoch - 1, step)
+            save_checkpoint(ckpt_path, model, trainer, epoch if epoch_done else epoch - 1, step, best_metric)
         if stopped:
             break
     if world > 1:
