@@ -172,6 +172,59 @@ for it in range(rounds):
         ref = F.relu(A.float() @ B.float().t() + bias + (res.float() if res is not None else 0))
         assert T.rel(Cm, ref) < T.TOL[torch.bfloat16], ('c1s', M, N, K, used, T.rel(Cm, ref))
     run('c1s_plain', c1s_case)
+# exact-arithmetic checks (tests/exact_cases.py: integer operands, torch.equal against float64) on random shapes: GEMMs under the default
+# dispatch and with each family forced, every layout, accumulate x split x {workspace, atomics}; convolutions forward / backward-data /
+# weight gradient.  gemm_case / conv_case pick the integer ranges that keep the precondition; the check functions assert it.
+import tests.exact_cases as E
+
+
+def exact_gemm():
+    M = rng.choice([rng.randint(1, 8), rng.randint(9, 700), rng.randint(700, 12000)])
+    N = rng.choice([rng.randint(1, 300), 8 * rng.randint(1, 300), 128 * rng.randint(1, 16)])
+    K = rng.choice([rng.randint(1, 400), 8 * rng.randint(1, 400), 64 * rng.randint(1, 48)])
+    form = rng.choice(['plain', 'epi', 'drop', 'acc', 'precise'])
+    la, lb = rng.choice(E.LAYOUTS)
+    kw = dict(la=la, lb=lb, pad=rng.choice([0, 8]), seed=rng.randint(0, 1000))
+    if form == 'epi':
+        kw.update(epi=True, alpha=rng.choice(E.ALPHAS), act=rng.choice([E.ACT_NONE, E.ACT_RELU]), batch=rng.choice([1, 1, 3]))
+    elif form == 'drop':
+        kw.update(drop=True, act=rng.choice([E.ACT_NONE, E.ACT_RELU]))
+    elif form == 'acc':
+        kw.update(acc=True, split_k=rng.choice([1, 3, 8]), ws=rng.random() < 0.5, rowsum=kw['la'] == E.TRANS and kw['lb'] == E.TRANS)
+    elif form == 'precise':
+        kw.update(precise=rng.choice(['A', 'B']))
+        K = min(K, 1000)                                   # 1000 * 2047 * 7 < 2^24
+    else:
+        kw.update(out=rng.choice([E.BF, E.F32]))
+    opts = rng.choice([{}, {}, dict(GLDS=0, PIPE=0, SKINNY=0), dict(GLDS=2, PIPE=0, SKINNY=0), dict(GLDS=3, PIPE=0, SKINNY=0), dict(SKINNY=2, GLDS=0),
+                       dict(PIPE=100 + rng.randint(0, 7), SKINNY=0), dict(C1S=2)])
+    prev = {n: h.set_option(getattr(h, 'OPT_' + n), v) for n, v in opts.items()}
+    try:
+        E.check_gemm(h, E.gemm_case('fuzz', M, N, K, **kw))
+    finally:
+        for n, v in prev.items():
+            h.set_option(getattr(h, 'OPT_' + n), v)
+
+
+def exact_conv():
+    Cin, Cout = rng.choice([64, 128, 256, 512]), rng.choice([64, 128, 256, 512])
+    k = rng.choice([1, 3])
+    opts = rng.choice([{}, {}, dict(GLDS=0, PIPE=0, SKINNY=0), dict(GLDS=rng.choice([2, 3]), PIPE=0), dict(PIPE=100 + rng.randint(0, 5)), dict(C1S=2), dict(C3S=2),
+                       dict(C3_HALO=2), dict(GLDS_WGRAD=rng.choice([0, 2]))])
+    c = E.conv_case('fuzz', Cin, Cout, k, rng.choice([1, 2]), k // 2, rng.randint(6, 48), rng.randint(6, 64), rng.randint(1, 6), seed=rng.randint(0, 1000),
+                    res=rng.random() < 0.5, mask=rng.random() < 0.5, split_k=rng.choice([0, 0, 4]))
+    prev = {n: h.set_option(getattr(h, 'OPT_' + n), v) for n, v in opts.items()}
+    try:
+        E.check_conv(h, c)
+    finally:
+        for n, v in prev.items():
+            h.set_option(getattr(h, 'OPT_' + n), v)
+
+
+for it in range(rounds):
+    run('exact_gemm', exact_gemm)
+    run('exact_gemm', exact_gemm)
+    run('exact_conv', exact_conv)
 print('fuzz done: %d failures (%d attention shapes refused as out of range)' % (len(fails), out_of_range))
 for f in fails:
     print(f)
