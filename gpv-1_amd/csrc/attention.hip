@@ -36,7 +36,6 @@ struct AttnK {
 // element (drop probability floor(p * 65536) / 65536), mixed from the row's seed with full-rate VALU only (shifts, xors, 24-bit
 // multiplies).  The 64-bit counter hash of common.h per SCORE (three quarter-rate 32-bit multiplies) made the dh = 32 kernels
 // spend more on the mask than on the softmax; forward, dQ and dK/dV kernels must agree on this function.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t ATTN_PAIR_STEP = 0x9E3779B9u;
 __device__ __forceinline__ uint32_t attn_row_seed(uint64_t seed, uint64_t row) { return hash_u32(seed, row); }
 __device__ __forceinline__ uint32_t attn_pair_bits(uint32_t x) {     // x = row seed + pair index * ATTN_PAIR_STEP
@@ -79,8 +78,8 @@ template <typename T> struct R8 {  // 8 staged values as floats
 };
 
 // 8 consecutive elements as loaded (16 bytes of bf16, 32 of fp32): what a thread holds while a batch of staging loads is in flight
-template <typename T> struct Raw8;
-template <> struct Raw8<bf16> {
+template <typename T> struct AttnRaw8;
+template <> struct AttnRaw8<bf16> {
   bf16x8 r;
   __device__ __forceinline__ void zero() { r = bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
   __device__ __forceinline__ void load(const bf16* p) { r = *reinterpret_cast<const bf16x8*>(p); }
@@ -91,7 +90,7 @@ template <> struct Raw8<bf16> {
     return x;
   }
 };
-template <> struct Raw8<float> {
+template <> struct AttnRaw8<float> {
   float v[8];
   __device__ __forceinline__ void zero() {
 #pragma unroll
@@ -115,7 +114,7 @@ template <> struct Raw8<float> {
 // (seen in the ISA) -- "all loads first" was several dependent round trips.
 template <typename T, int DH, int MAXR, int NTHR> struct RowBatch {      // [rows][DH] row-major -> LDS [rows_pad][DH + 8]
   static constexpr int SL = DH / 8, IT = (MAXR * SL + NTHR - 1) / NTHR;
-  Raw8<T> x[IT];
+  AttnRaw8<T> x[IT];
   int rv_, dh_;
   __device__ __forceinline__ void load(const T* g, int64_t rs, int rows_valid, int rows_pad, int dh) {
     rv_ = rows_valid; dh_ = dh;
@@ -141,7 +140,7 @@ template <typename T, int DH, int MAXR, int NTHR> struct RowBatch {      // [row
 };
 template <typename T, int DH, int MAXR, int NTHR> struct ColBatch {      // transposed: LDS [DH][pitch], element (d, r) = g[r][d]
   static constexpr int DG = DH / 8, IT = ((MAXR / 2) * DG + NTHR - 1) / NTHR;
-  Raw8<T> a[IT], b[IT];
+  AttnRaw8<T> a[IT], b[IT];
   int rv_;
   __device__ __forceinline__ void load(const T* g, int64_t rs, int rows_valid, int rows_pad) {
     const int np = rows_pad / 2;
@@ -248,8 +247,7 @@ __global__ __launch_bounds__(QTHR) void attn_q_kernel(AttnK p) {
   int b, h, xs;
   {
     const int nsp = p.nsplit, total = (int)gridDim.x;
-    const int qd = total >> 3, r = total & 7, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
-    const int v = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + loc;
+    const int v = xcd_contiguous((int)blockIdx.x, total);
     xs = v % nsp;
     const int bh = v / nsp;
     h = bh % p.H; b = bh / p.H;
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(QTHR) void attn_q_kernel(AttnK p) {
   const int per = (nqt + p.nsplit - 1) / p.nsplit;
   const int qt_end = min(nqt, (xs + 1) * per);
   const int qt_first = xs * per + wave;
-  Raw8<T> nq[KC], nd[MODE ? KC : 1], no[MODE ? KC : 1];
+  AttnRaw8<T> nq[KC], nd[MODE ? KC : 1], no[MODE ? KC : 1];
   float nlse = 0.f;
   // Unconditional loads (round 5): a tile / row beyond the range re-reads the LAST query row -- such rows are never stored -- and the
   // zero padding of the head dimension (dh = 48 in a 64-wide fragment) is applied where the fragment is USED.  With `if (ok) load; else
@@ -614,8 +612,7 @@ __global__ __launch_bounds__(QTHR) void attn_qkv_kernel(AttnK p, QkvK xk) {
   int b, h;
   {
     const int total = (int)gridDim.x;
-    const int qd = total >> 3, r = total & 7, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
-    const int v = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + loc;     // contiguous (batch, head) range per XCD: the heads of an image share x
+    const int v = xcd_contiguous((int)blockIdx.x, total);     // contiguous (batch, head) range per XCD: the heads of an image share x
     h = v % p.H; b = v / p.H;
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
@@ -1011,8 +1008,7 @@ __global__ __launch_bounds__(QTHR) void attn_kv2_kernel(AttnK p) {
   int b, h, xs;
   {
     const int nsp = p.nsplit, total = (int)gridDim.x;
-    const int qd = total >> 3, r = total & 7, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
-    const int v = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + loc;
+    const int v = xcd_contiguous((int)blockIdx.x, total);
     xs = v % nsp;
     const int bh = v / nsp;
     h = bh % p.H; b = bh / p.H;
@@ -1023,7 +1019,7 @@ __global__ __launch_bounds__(QTHR) void attn_kv2_kernel(AttnK p) {
   const int kt_end = min(nkt, (xs + 1) * per);
   const int kt_first = xs * per + wave;
   // this wave's K / V rows (MFMA B operands), fetched one key tile ahead
-  Raw8<T> nk[KC], nv[KC];
+  AttnRaw8<T> nk[KC], nv[KC];
   bool ndead = true;
   auto fetch = [&](int kt_) {
     const int key_ = kt_ * 16 + (lane & 15);
@@ -1188,8 +1184,7 @@ __global__ __launch_bounds__(QTHR) void attn_bwd1_kernel(AttnK p) {
   int b, h;
   {
     const int total = (int)gridDim.x;
-    const int qd = total >> 3, r = total & 7, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
-    const int bh = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + loc;
+    const int bh = xcd_contiguous((int)blockIdx.x, total);
     h = bh % p.H; b = bh / p.H;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
@@ -1206,7 +1201,7 @@ __global__ __launch_bounds__(QTHR) void attn_bwd1_kernel(AttnK p) {
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int d0 = kc * 32 + g * 8;
-      Raw8<T> a, c;
+      AttnRaw8<T> a, c;
       if (ok && d0 < p.dh) { a.load(kg + (int64_t)key_ * p.k_rs + d0); c.load(vg + (int64_t)key_ * p.v_rs + d0); } else { a.zero(); c.zero(); }
       kh[j][kc] = a.r; vh[j][kc] = c.r;
     }
@@ -1593,8 +1588,7 @@ __global__ __launch_bounds__(QTHR) void attn_long_kernel(AttnK p) {
   int b, h, xs;
   {                                                // (XCD-contiguous (batch, head, query block) ranges, as in attn_q_kernel)
     const int nsp = p.nsplit, total = (int)gridDim.x;
-    const int qd = total >> 3, r = total & 7, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
-    const int v = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + loc;
+    const int v = xcd_contiguous((int)blockIdx.x, total);
     xs = v % nsp;
     const int bh = v / nsp;
     h = bh % p.H; b = bh / p.H;
@@ -1898,8 +1892,7 @@ __global__ __launch_bounds__(QTHR) void attn_kvl_kernel(AttnK p) {
   int b, h, xs;
   {
     const int nsp = p.nsplit, total = (int)gridDim.x;
-    const int qd = total >> 3, r = total & 7, xcd = (int)blockIdx.x & 7, loc = (int)blockIdx.x >> 3;
-    const int v = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + loc;
+    const int v = xcd_contiguous((int)blockIdx.x, total);
     xs = v % nsp;
     const int bh = v / nsp;
     h = bh % p.H; b = bh / p.H;
@@ -1936,7 +1929,7 @@ __global__ __launch_bounds__(QTHR) void attn_kvl_kernel(AttnK p) {
   const T* og = reinterpret_cast<const T*>(p.o) + b * p.o_bs + h * p.dh;
   RowBatch<T, DHK, QC, QTHR> qr, dr;
   ColBatch<T, DHV, QC, QTHR> qcb, dcb;
-  Raw8<T> ua[NDC], wa[NDC];                        // delta: query row tid / TPQ, column groups tid % TPQ + TPQ m
+  AttnRaw8<T> ua[NDC], wa[NDC];                        // delta: query row tid / TPQ, column groups tid % TPQ + TPQ m
   float nls = 0.f;
   const int dr_ = tid / TPQ, dsub = tid % TPQ;
   auto load = [&](int c) {

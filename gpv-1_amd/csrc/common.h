@@ -27,6 +27,54 @@ static inline int tune_env(const char*, int dflt) { return dflt; }
     if (e_ != hipSuccess) return (int)e_; \
   } while (0)
 
+// 16-byte alignment of an operand base: the precondition of every 16-byte vector access and of the LDS-DMA loaders
+__host__ __device__ __forceinline__ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// XCD-aware work order: workgroup b runs on XCD b % 8 (observed dispatch rule, used for speed only).  Give every
+// XCD a CONTIGUOUS range of tiles so that the column tiles of one row panel (same A rows / same conv pixels) share
+// one L2 instead of being fetched from HBM once per XCD.  Bijective for any grid size: workgroup `bid` of `nwg` -> item.
+// With a split reduction (gridDim.y > 1) the GEMM kernels remap the (tile, split) plane as a whole, split-major: an XCD then
+// runs ALL tiles of one reduction slice together, so the slice's dy / x rows are fetched from HBM once and shared
+// through that XCD's L2 (wgrad of a 1x1 conv has only 4..32 output tiles: tile-only remapping left every XCD
+// with one tile and all slices, i.e. no sharing at all: TCC hit rate 0.6 %).
+__device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
+// Accumulator-order channel map of the kernels that finish their outputs in registers: LDS row (= staged weight row / output column) L of
+// a 32-row group holds channel 8 (r / 4) + 4 jj + (r % 4), jj = L / 16 % 2, r = L % 16, so that the MFMA tiles 2 t, 2 t + 1 leave lane
+// (row, g) with the 8 CONSECUTIVE channels 32 t + 8 g .. + 7 of its row: bias / residual / mask / output are plain 16-byte accesses.
+// NH > 0: NH channels per register pass, pass h = L / NH keeps its own NH channels; NH = 0: one pass (L < its channel count)
+template <int NH = 0>
+__device__ __forceinline__ int acc_chan(int L) {
+  int h = 0;
+  if constexpr (NH != 0) h = L / NH;
+  const int w = L - h * NH, j = w >> 4, r = w & 15;      // pass h, then MFMA tile j and row r inside it
+  return h * NH + (j >> 1) * 32 + (r >> 2) * 8 + (j & 1) * 4 + (r & 3);
+}
+
+// (y > 0) of eight STORED bf16 values (four dwords) as one byte, bit e = element e -- as 16-bit integers: > 0 (a stored -0 or negative
+// is not; what a later (float)mask > 0.f test sees) -- in 13 instructions: packed min(., 1) / max(., 0) leave 0 | 1 per half, a byte
+// permute gathers four halves' low bytes, a 4 x 8-bit dot product with (1, 2, 4, 8) makes the nibble.
+// Inline asm because of a hipcc 7.2 miscompile: written with __builtin_elementwise_min / max on short2 values the compiler
+// derived all four words' flags from the FIRST word -- v_cmp_lt_i16 on elements 0 and 1 only, seen in the ISA -- and every byte came out
+// as 0x00 / 55 / aa / ff.  A fix or a compiler upgrade has this one place to change.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint32_t positive_bits8(u32x4 w) {
+  const uint32_t one2 = 0x00010001u, zero2 = 0u;
+  uint32_t m[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    uint32_t tq;
+    asm("v_pk_min_i16 %0, %1, %2" : "=v"(tq) : "v"(w[q]), "v"(one2));
+    asm("v_pk_max_i16 %0, %1, %2" : "=v"(m[q]) : "v"(tq), "v"(zero2));
+  }
+  const uint32_t b03 = __builtin_amdgcn_perm(m[1], m[0], 0x06040200u);      // bytes (m0.b0, m0.b2, m1.b0, m1.b2) = elements 0..3
+  const uint32_t b47 = __builtin_amdgcn_perm(m[3], m[2], 0x06040200u);
+  return __builtin_amdgcn_udot4(b03, 0x08040201u, 0u, false) | (__builtin_amdgcn_udot4(b47, 0x08040201u, 0u, false) << 4);
+}
+
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }
 
@@ -133,7 +181,7 @@ __device__ __forceinline__ void stage_chunks16(int total, int tid, SrcF src, Dst
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
-template <typename T> struct Ld8;   // load 8 consecutive elements as float[8]
+template <typename T> struct Ld8;   // load / store 8 consecutive elements as float[8]
 template <> struct Ld8<bf16> {
   static __device__ __forceinline__ void ld(const bf16* p, float* o) {
     bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
@@ -146,6 +194,18 @@ template <> struct Ld8<bf16> {
     for (int i = 0; i < 8; ++i) v[i] = (bf16)o[i];
     *reinterpret_cast<bf16x8*>(p) = v;
   }
+  // non-temporal forms (streaming: do not displace what the next kernels will read from L2 / MALL)
+  static __device__ __forceinline__ void ld_nt(const bf16* p, float* o) {
+    const bf16x8 v = __builtin_bit_cast(bf16x8, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = (float)v[i];
+  }
+  static __device__ __forceinline__ void st_nt(bf16* p, const float* o) {
+    bf16x8 v;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (bf16)o[i];
+    __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), reinterpret_cast<u32x4*>(p));
+  }
 };
 template <> struct Ld8<float> {
   static __device__ __forceinline__ void ld(const float* p, float* o) {
@@ -157,6 +217,8 @@ template <> struct Ld8<float> {
     *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
     *reinterpret_cast<float4*>(p + 4) = make_float4(o[4], o[5], o[6], o[7]);
   }
+  static __device__ __forceinline__ void ld_nt(const float* p, float* o) { ld(p, o); }     // (fp32 outputs have no streaming launches)
+  static __device__ __forceinline__ void st_nt(float* p, const float* o) { st(p, o); }
 };
 
 __device__ __forceinline__ float wave_sum(float v) {

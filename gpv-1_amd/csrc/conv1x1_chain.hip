@@ -16,7 +16,6 @@
 namespace gpvk {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct ChainK {
   const void* a1; const void* a2; const void* w1; const void* w2; const float* bias; const void* res; void* y;
@@ -26,12 +25,6 @@ struct ChainK {
   int nt;
   void* zbits;                    // round 6: (z > 0) as one bit per element, N2 = 128: bit c & 7 of byte 4 ((c % 32) / 8) + c / 32 of the pixel's 16 (gpv_conv_args.y_mask_bits' order for 128 channels), or NULL
 };
-
-template <int NH>
-__device__ __forceinline__ int c1c_chan(int L) {      // (conv1x1_stream.hip c1s_chan)
-  const int hh = L / NH, w = L - hh * NH, j = w >> 4, r = w & 15;
-  return hh * NH + (j >> 1) * 32 + (r >> 2) * 8 + (j & 1) * 4 + (r & 3);
-}
 
 // K1 = 64 channels of a1 (+ K2 = 64 of a2: the downsample branch of a stage's first block), N = 256, N2 = 64 | 128
 template <int K1, int K2, int N2, bool RES, bool BITS = false>
@@ -75,11 +68,11 @@ __global__ __launch_bounds__(512) void c1c_kernel(ChainK p) {
     const bf16* W2 = reinterpret_cast<const bf16*>(p.w2);
     const bf16* WN = reinterpret_cast<const bf16*>(p.wn);
     stage_chunks16<512, 8>(N * SL, tid,
-        [&](int idx) { const int L = idx / SL, sl = idx - L * SL; const int c = c1c_chan<N>(L);
+        [&](int idx) { const int L = idx / SL, sl = idx - L * SL; const int c = acc_chan<N>(L);
                        return sl < SL1 ? W1 + (int64_t)c * K1 + sl * 8 : W2 + (int64_t)c * K2 + (sl - SL1) * 8; },
         [&](int idx) { const int L = idx / SL, sl = idx - L * SL; return Wl + L * KP + sl * 8; });
     stage_chunks16<512, 8>(N2 * SL2, tid,
-        [&](int idx) { const int L = idx / SL2, sl = idx - L * SL2; return WN + (int64_t)c1c_chan<N2>(L) * N + sl * 8; },
+        [&](int idx) { const int L = idx / SL2, sl = idx - L * SL2; return WN + (int64_t)acc_chan<N2>(L) * N + sl * 8; },
         [&](int idx) { const int L = idx / SL2, sl = idx - L * SL2; return Wn + L * KP2 + sl * 8; });
     for (int c = tid; c < N; c += 512) bias_l[c] = p.bias ? p.bias[c] : 0.f;
     for (int c = tid; c < N2; c += 512) bias_n[c] = p.bias_n ? p.bias_n[c] : 0.f;
@@ -159,18 +152,7 @@ __global__ __launch_bounds__(512) void c1c_kernel(ChainK p) {
       for (int e = 0; e < 8; ++e) o[e] = (bf16)fmaxf(v[e], 0.f);
       if (pok) *reinterpret_cast<bf16x8*>(Z + (int64_t)px * N2 + c0) = o;
       if constexpr (BITS) {
-        // (z > 0) of the stored bf16 values, eight into a byte (conv1x1_stream.hip: packed min / max as inline asm, byte permute, 4 x 8-bit dot)
-        const u32x4 ow = __builtin_bit_cast(u32x4, o);
-        const uint32_t one2 = 0x00010001u, zero2 = 0u;
-        uint32_t mq[4];
-#pragma unroll
-        for (int q2 = 0; q2 < 4; ++q2) {
-          uint32_t tq;
-          asm("v_pk_min_i16 %0, %1, %2" : "=v"(tq) : "v"(ow[q2]), "v"(one2));
-          asm("v_pk_max_i16 %0, %1, %2" : "=v"(mq[q2]) : "v"(tq), "v"(zero2));
-        }
-        const uint32_t b03 = __builtin_amdgcn_perm(mq[1], mq[0], 0x06040200u), b47 = __builtin_amdgcn_perm(mq[3], mq[2], 0x06040200u);
-        zb |= (__builtin_amdgcn_udot4(b03, 0x08040201u, 0u, false) | (__builtin_amdgcn_udot4(b47, 0x08040201u, 0u, false) << 4)) << (u * 8);
+        zb |= positive_bits8(__builtin_bit_cast(u32x4, o)) << (u * 8);      // (z > 0) of the stored bf16 values, eight into a byte (common.h)
       }
     }
     if constexpr (BITS) {

@@ -16,7 +16,6 @@
 namespace gpvk {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct DualK {
   const void* a1; const void* a2; const void* w1; const void* w2; const float* bias; void* y;
@@ -26,12 +25,6 @@ struct DualK {
   int relu, nt;
   void* bits;                     // round 6: (y > 0) as one bit per element in conv1x1_stream.hip's byte order (gpv_conv_args.y_mask_bits), or NULL
 };
-
-template <int NH>
-__device__ __forceinline__ int c1d_chan(int L) {      // (conv1x1_stream.hip c1s_chan)
-  const int hh = L / NH, w = L - hh * NH, j = w >> 4, r = w & 15;
-  return hh * NH + (j >> 1) * 32 + (r >> 2) * 8 + (j & 1) * 4 + (r & 3);
-}
 
 template <int K1, int K2, int NH, bool NT, bool BITS = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void c1d_kernel(DualK p, int ncols) {
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bf16* W1 = reinterpret_cast<const bf16*>(p.w1);
     const bf16* W2 = reinterpret_cast<const bf16*>(p.w2);
     stage_chunks16<512, 8>(ncols * SL, tid,
-        [&](int idx) { const int L = idx / SL, sl = idx - L * SL; const int c = cbase + c1d_chan<NH>(L);
+        [&](int idx) { const int L = idx / SL, sl = idx - L * SL; const int c = cbase + acc_chan<NH>(L);
                        return sl < SL1 ? W1 + (int64_t)c * K1 + sl * 8 : W2 + (int64_t)c * K2 + (sl - SL1) * 8; },
         [&](int idx) { const int L = idx / SL, sl = idx - L * SL; return Wl + L * KP + sl * 8; });
     for (int c = tid; c < ncols; c += 512) bias_l[c] = p.bias ? p.bias[cbase + c] : 0.f;
@@ -148,17 +141,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if constexpr (NT) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" :: "v"(q), "v"(ov) : "memory");
         else asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(q), "v"(ov) : "memory");
         if constexpr (BITS) {
-          // (output > 0) of the stored bf16 values, eight into a byte (conv1x1_stream.hip: packed min / max as inline asm, byte permute, 4 x 8-bit dot)
-          const uint32_t one2 = 0x00010001u, zero2 = 0u;
-          uint32_t mq[4];
-#pragma unroll
-          for (int q2 = 0; q2 < 4; ++q2) {
-            uint32_t tq;
-            asm("v_pk_min_i16 %0, %1, %2" : "=v"(tq) : "v"(ov[q2]), "v"(one2));
-            asm("v_pk_max_i16 %0, %1, %2" : "=v"(mq[q2]) : "v"(tq), "v"(zero2));
-          }
-          const uint32_t b03 = __builtin_amdgcn_perm(mq[1], mq[0], 0x06040200u), b47 = __builtin_amdgcn_perm(mq[3], mq[2], 0x06040200u);
-          bits_acc |= (__builtin_amdgcn_udot4(b03, 0x08040201u, 0u, false) | (__builtin_amdgcn_udot4(b47, 0x08040201u, 0u, false) << 4)) << (t * 8);
+          bits_acc |= positive_bits8(ov) << (t * 8);      // (output > 0) of the stored bf16 values, eight into a byte (common.h)
         }
       }
       if constexpr (BITS) {

@@ -20,17 +20,10 @@
 namespace gpvk {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 mfma16s(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
-// LDS row L of the staged weight matrix holds output channel chan(L): pass h = L / NH (NH channels per register pass), MFMA
-// tile j = (L % NH) / 16, row r = L % 16 -> channel h NH + 32 (j / 2) + 8 (r / 4) + 4 (j & 1) + (r % 4)
-template <int NH>
-__device__ __forceinline__ int c1s_chan(int L) {
-  const int h = L / NH, w = L - h * NH, j = w >> 4, r = w & 15;
-  return h * NH + (j >> 1) * 32 + (r >> 2) * 8 + (j & 1) * 4 + (r & 3);
-}
+// LDS row L of the staged weight matrix holds output channel acc_chan<NH>(L) (common.h): NH channels per register pass
 
 // LIN: the kernel as a plain linear layer's GEMM (gpv_gemm, K = 256 -> 2048 outputs: the DETR feed-forward 256 -> 2048 and its
 // backward-data product with the ReLU mask): alpha on the accumulator and the GEMM kernels' dropout
@@ -104,7 +97,7 @@ void c1s_kernel(GemmK p, int ncols) {
     for (int i = wv; i < ninst; i += 8) {
       const int L = i * R + (R > 1 ? lane / SPR : 0), sl = lane % SPR;
       const int sw = K >= 128 ? (L & 15) : ((L >> 1) & 7);
-      const int voff = (c1s_chan<NH>(L) * (int)p.ldb + ((sl ^ sw) * 8)) * 2;
+      const int voff = (acc_chan<NH>(L) * (int)p.ldb + ((sl ^ sw) * 8)) * 2;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_void_t*)(smem_raw + i * 1024), 16, voff, 0, 0, 0);
     }
   }
@@ -276,24 +269,7 @@ void c1s_kernel(GemmK p, int ncols) {
           }
         }
         if constexpr (BITS && !MASK) {
-          // (output > 0) of the STORED bf16 values -- as 16-bit integers: > 0 (a stored -0 or negative is not; what a later
-          // (float)mask > 0.f test sees) -- eight of them into one byte in 13 instructions: packed min(., 1) / max(., 0) leave 0 | 1 per
-          // half, a byte permute gathers four halves' low bytes, a 4 x 8-bit dot product with (1, 2, 4, 8) makes the nibble
-          // (inline asm: written with __builtin_elementwise_min / max on short2 values hipcc 7.2 derived all four words' flags from
-          //  the FIRST word -- v_cmp_lt_i16 on elements 0 and 1 only, seen in the ISA -- and every byte came out as 0x00 / 55 / aa / ff)
-          const u32x4 ow = __builtin_bit_cast(u32x4, o);
-          const uint32_t one2 = 0x00010001u, zero2 = 0u;
-          uint32_t m[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            uint32_t tq;
-            asm("v_pk_min_i16 %0, %1, %2" : "=v"(tq) : "v"(ow[q]), "v"(one2));
-            asm("v_pk_max_i16 %0, %1, %2" : "=v"(m[q]) : "v"(tq), "v"(zero2));
-          }
-          const uint32_t b03 = __builtin_amdgcn_perm(m[1], m[0], 0x06040200u);      // bytes (m0.b0, m0.b2, m1.b0, m1.b2) = elements 0..3
-          const uint32_t b47 = __builtin_amdgcn_perm(m[3], m[2], 0x06040200u);
-          const uint32_t byte = __builtin_amdgcn_udot4(b03, 0x08040201u, 0u, false) | (__builtin_amdgcn_udot4(b47, 0x08040201u, 0u, false) << 4);
-          bits_acc[t >> 2] |= byte << ((t & 3) * 8);
+          bits_acc[t >> 2] |= positive_bits8(__builtin_bit_cast(u32x4, o)) << ((t & 3) * 8);      // (output > 0) of the STORED bf16 values (common.h)
         }
         // No branch and no store hipcc can see in the tile loop (conv1x1_dual.hip): rows beyond M were LOADED from row M - 1 (A,
         // residual, mask, dropout index), so they hold row M - 1's results and store them there again; the store is inline asm because
@@ -405,8 +381,6 @@ int c1s_n(const GemmK& k, hipStream_t st, bool linear) {
   return -1;
 }
 
-inline bool al16s(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 int g_c1s_mode = 1;          // 0 never, 1 heuristic, 2 wherever legal (tests)
@@ -426,7 +400,7 @@ int c1s_try_launch(const GemmK& k, int dtype_in, int dtype_out, hipStream_t st, 
   if (linear && (k.cg.SH == 2 || k.cg.cm || k.nt_io)) return -1;
   if (k.act != GPV_ACT_NONE && k.act != GPV_ACT_RELU) return -1;
   if (k.lda % 8 || k.ldb != k.K || k.ldc % 8 || (k.res && k.ldr % 8) || (k.mask && k.ldm % 8)) return -1;
-  if (!al16s(k.A) || !al16s(k.B) || !al16s(k.C) || (k.res && !al16s(k.res)) || (k.mask && !al16s(k.mask))) return -1;
+  if (!al16(k.A) || !al16(k.B) || !al16(k.C) || (k.res && !al16(k.res)) || (k.mask && !al16(k.mask))) return -1;
   if (linear) {      // gpv_gemm: 256 -> 2048 features over >= 2048 rows (the DETR feed-forward; tools/bench_c1s_linear.py: 1024 / 1536 outputs are faster on the tile kernels)
     if (mode == 1 && (k.K != 256 || k.N < 1536 || k.M < 2048)) return -1;      // (1536: as graph nodes 20.8 against 26.8 us at 9600 rows, tools/tune_gemms.py --chain; 1024 stays on the tile kernels)
   } else if (mode == 1 && ((int64_t)k.M * nsl < 65536 || k.M < 32768)) return -1;   // a streaming regime needs rows (x slices): the layer1-3 maps at training batch sizes

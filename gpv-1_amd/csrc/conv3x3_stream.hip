@@ -24,7 +24,6 @@
 namespace gpvk {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int C3_OOB = 0x7ffffff0;
@@ -436,8 +435,6 @@ int c3r_mode(const GemmK& k, bool dgrad, hipStream_t st) {
   return m ? c3r_launch<CIN, false, true>(k, st) : c3r_launch<CIN, false, false>(k, st);
 }
 
-inline bool al16c(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 int g_c3s_mode = 1;          // 0 never, 1 heuristic, 2 wherever legal (tests)
@@ -455,7 +452,7 @@ int c3s_try_launch(const GemmK& k, int dtype_in, int dtype_out, hipStream_t st, 
   if (g.Cs % 8 != 0 || k.ldc % 8 != 0 || (k.mask && k.ldm % 8 != 0) || k.ldb != k.K) return -1;
   if (k.res || k.rowscale || k.alpha != 1.0f || k.dthresh || k.accumulate || k.split_k > 1 || k.a_rowsum) return -1;
   if (k.act != GPV_ACT_NONE && k.act != GPV_ACT_RELU) return -1;
-  if (!al16c(k.A) || !al16c(k.B) || !al16c(k.C) || (k.mask && !al16c(k.mask))) return -1;
+  if (!al16(k.A) || !al16(k.B) || !al16(k.C) || (k.mask && !al16(k.mask))) return -1;
   const bool d2 = g.SH == 2 && g.dgrad && g.Cin == 128 && g.OH == 2 * g.IH && g.OW == 2 * g.IW && k.act == GPV_ACT_NONE && !k.bias;
   if (g.SH != 1 && !d2) return -1;       // (the stride-2 forward stays on the tile kernels)
   // input extent addressed with 32-bit byte offsets (dgrad: the "input" is dy)

@@ -13,7 +13,7 @@
 //     kernel (64 VGPRs);
 //   * the first product is computed TRANSPOSED, C1[f][m] = W1c[f][:] . x[m][:]  -- the accumulator tiles 2u, 2u + 1 then leave lane
 //     (m, g) with 8 hidden features of its row m, and because W1's rows are staged PERMUTED (LDS row 16 j + 4 a + b of a 32-row group
-//     holds feature 8 a + 4 j + b: conv1x1_stream.hip's c1s_chan) they are the 8 CONSECUTIVE features 8 g .. 8 g + 7: after bias /
+//     holds feature 8 a + 4 j + b: common.h acc_chan) they are the 8 CONSECUTIVE features 8 g .. 8 g + 7: after bias /
 //     ReLU / dropout / rounding that is one 16-byte store of h AND, unchanged, the B fragment (k = 8 g .. + 7) of the second
 //     product's MFMA -- the hidden activation goes from accumulator to operand without touching LDS (conv1x1_chain.hip's trick);
 //   * the weights stream L2 -> LDS with buffer_load ... lds (no staging registers), two stages of 64 KB: chunk t + 1 is in flight
@@ -41,7 +41,6 @@ namespace gpvk {
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void_t;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct FfnK {
   const void* x; const void* w1; const float* b1; const void* w2; const float* b2; const float* gamma; const float* beta;
@@ -53,10 +52,6 @@ struct FfnK {
 
 constexpr int D = 256, BM = 64, FC = 64, MAXF = 8192;
 constexpr int W1C_BYTES = FC * D * 2, W2C_BYTES = D * FC * 2, STAGE = W1C_BYTES + W2C_BYTES;      // 32 KB + 32 KB
-
-__device__ __forceinline__ int perm32(int r) {      // LDS row r of a 32-row group -> the source row it holds
-  return (r & ~31) + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3);
-}
 
 // drop_mask<8> (common.h) for an EVEN flat index below 2^33, from the running word xb = (index / 2) * 0x9E3779B9 + seed terms: the four
 // pair hashes of drop_pair_bits without its two 32-bit multiplies (quarter rate: 16 cycles each on a wave that has nothing to hide
@@ -96,13 +91,13 @@ __global__ __launch_bounds__(256) void ffn_fwd_kernel(FfnK p) {
   const auto rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), (short)0, OOB, 0x00020000);
   const auto rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w2), (short)0, OOB, 0x00020000);
   const int lrow = lane >> 3, lchunk = (lane & 7) ^ lrow;
-  // W1 chunk: four k-panels (64 of the 256 input features each) of [64 rows][128 B]; wave w stages panel w.  Row L <- feature perm32(L)
-  // W2 chunk: [256 rows = output columns][128 B = the chunk's 64 features]; wave w stages rows 64 w .. + 63.  Row L <- column perm32(L)
+  // W1 chunk: four k-panels (64 of the 256 input features each) of [64 rows][128 B]; wave w stages panel w.  Row L <- feature depi_col_perm(L)
+  // W2 chunk: [256 rows = output columns][128 B = the chunk's 64 features]; wave w stages rows 64 w .. + 63.  Row L <- column depi_col_perm(L)
   int v1[8], v2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    v1[j] = (perm32(j * 8 + lrow) * D + wave * 64 + lchunk * 8) * 2;
-    v2[j] = (perm32(wave * 64 + j * 8 + lrow) * F + lchunk * 8) * 2;
+    v1[j] = (depi_col_perm(j * 8 + lrow) * D + wave * 64 + lchunk * 8) * 2;
+    v2[j] = (depi_col_perm(wave * 64 + j * 8 + lrow) * F + lchunk * 8) * 2;
   }
   auto issue = [&](int t, int stage) {
     unsigned char* s1 = smem + stage * STAGE + wave * 8192;

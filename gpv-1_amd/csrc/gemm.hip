@@ -140,7 +140,6 @@ struct KStage {
     Raw8<T>(&raw)[NIT] = bf.raw; bool(&okf)[NIT] = bf.okf;
     const int tid = threadIdx.x;
     if constexpr (BUF) {
-      typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
       const bool full = k0 + BK <= K;                      // uniform; K % 8 == 0 or finite padding (host): whole chunks
 #pragma unroll
       for (int it = 0; it < NIT; ++it) {
@@ -260,7 +259,6 @@ struct TStage {
   __device__ __forceinline__ void load(int k0, int K, const ConvGeom& g, Buf& bf) {
     Raw8<T>(&raw)[NIT] = bf.raw; bool(&okf)[NIT] = bf.okf;
     if constexpr (BUF) {
-      typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
       const bool full = k0 + BK <= K;                      // uniform
       const int soff = k0 * (int)ld * 2;
 #pragma unroll
@@ -347,32 +345,6 @@ struct TStage {
   }
 };
 
-template <typename T> struct Vec8IO;
-template <> struct Vec8IO<bf16> {
-  static __device__ __forceinline__ void ld(const bf16* p, float* o) { Ld8<bf16>::ld(p, o); }
-  static __device__ __forceinline__ void st(bf16* p, const float* o) { Ld8<bf16>::st(p, o); }
-  // non-temporal forms (streaming: do not displace what the next kernels will read from L2 / MALL)
-  static __device__ __forceinline__ void ld_nt(const bf16* p, float* o) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const bf16x8 v = __builtin_bit_cast(bf16x8, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = (float)v[i];
-  }
-  static __device__ __forceinline__ void st_nt(bf16* p, const float* o) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16)o[i];
-    __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), reinterpret_cast<u32x4*>(p));
-  }
-};
-template <> struct Vec8IO<float> {
-  static __device__ __forceinline__ void ld(const float* p, float* o) { Ld8<float>::ld(p, o); }
-  static __device__ __forceinline__ void st(float* p, const float* o) { Ld8<float>::st(p, o); }
-  static __device__ __forceinline__ void ld_nt(const float* p, float* o) { Ld8<float>::ld(p, o); }
-  static __device__ __forceinline__ void st_nt(float* p, const float* o) { Ld8<float>::st(p, o); }
-};
-
 template <typename TIn, typename TOut, int AMODE, int BMODE, int BM, int BN, bool VEC, bool NTIO = false>
 __device__ __forceinline__ void gemm_body(const GemmK& p) {
   constexpr bool PRECISE = sizeof(TIn) == 4;
@@ -384,20 +356,13 @@ __device__ __forceinline__ void gemm_body(const GemmK& p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  // XCD-aware tile order: workgroup b runs on XCD b % 8 (observed dispatch rule, used for speed only).  Give every
-  // XCD a CONTIGUOUS range of tiles so that the column tiles of one row panel (same A rows / same conv pixels) share
-  // one L2 instead of being fetched from HBM once per XCD.  Bijective for any grid size.
-  // With a split reduction (gridDim.y > 1) the (tile, split) plane is remapped as a whole, split-major: an XCD then
-  // runs ALL tiles of one reduction slice together, so the slice's dy / x rows are fetched from HBM once and shared
-  // through that XCD's L2 (wgrad of a 1x1 conv has only 4..32 output tiles: tile-only remapping left every XCD
-  // with one tile and all slices, i.e. no sharing at all: TCC hit rate 0.6 %).
+  // XCD-aware tile order (common.h xcd_contiguous); with a split reduction the (tile, split) plane is remapped as a whole, split-major
   int tile, ksplit;
   {
     const bool plane = gridDim.z == 1;
     const int gx = gridDim.x;
     const int nwg = plane ? gx * (int)gridDim.y : gx, bid = plane ? (int)blockIdx.x + gx * (int)blockIdx.y : (int)blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const int v = xcd_contiguous(bid, nwg);
     ksplit = plane ? v / gx : (int)blockIdx.y;
     tile = plane ? v - ksplit * gx : v;
   }
@@ -645,14 +610,14 @@ __device__ __forceinline__ void gemm_body(const GemmK& p) {
         const bool full = n + 8 <= p.N;
         const int64_t mp = (AMODE == OP_CONV && p.cg.cm && inb) ? s_rowpix[m - row0] : m;     // output pixel of this GEMM row
         if (Rp) {
-          if (inb && v_res && full) { if constexpr (NTIO) Vec8IO<TOut>::ld_nt(Rp + mp * p.ldr + n, rv[g]); else Vec8IO<TOut>::ld(Rp + mp * p.ldr + n, rv[g]); }
+          if (inb && v_res && full) { if constexpr (NTIO) Ld8<TOut>::ld_nt(Rp + mp * p.ldr + n, rv[g]); else Ld8<TOut>::ld(Rp + mp * p.ldr + n, rv[g]); }
           else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) rv[g][e] = (inb && n + e < p.N) ? (float)Rp[mp * p.ldr + n + e] : 0.f;
           }
         }
         if (Mp) {
-          if (inb && v_msk && full) Vec8IO<TOut>::ld(Mp + mp * p.ldm + n, mv[g]);
+          if (inb && v_msk && full) Ld8<TOut>::ld(Mp + mp * p.ldm + n, mv[g]);
           else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) mv[g][e] = (inb && n + e < p.N) ? (float)Mp[mp * p.ldm + n + e] : 0.f;
@@ -688,7 +653,7 @@ __device__ __forceinline__ void gemm_body(const GemmK& p) {
         }
         const int64_t mp = (AMODE == OP_CONV && p.cg.cm && m < p.M) ? s_rowpix[m - row0] : m;
         TOut* dst = Cp + mp * ldc + n;
-        if (v_st && full) { if constexpr (NTIO) Vec8IO<TOut>::st_nt(dst, v); else Vec8IO<TOut>::st(dst, v); }   // (a run-time choice: the two stores are merged and lose the hint)
+        if (v_st && full) { if constexpr (NTIO) Ld8<TOut>::st_nt(dst, v); else Ld8<TOut>::st(dst, v); }   // (a run-time choice: the two stores are merged and lose the hint)
         else {
 #pragma unroll
           for (int e = 0; e < 8; ++e)
@@ -865,12 +830,11 @@ __global__ __launch_bounds__(256) void conv_split_epilogue_kernel(const float* _
 // pixels): 12..40 tiles of a 128-wide kernel walk K = 1152..4608 alone on a 256-CU chip.  The reduction is split over grid.y
 // into fp32 slabs of the caller's workspace (64 x 64 tiles, ~300 workgroups of >= 8 k-tiles), a second launch sums the slabs and
 // applies bias / residual / ReLU.  Returns 0 = launched, -1 = not applicable.
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 int conv_split_try_launch(const GemmK& k, int dtype_in, int dtype_out, hipStream_t st) {
   static const int on = tune_env("GPV_CONV_SPLIT", 1);
   if (!on || g_kernel_forced || dtype_in != GPV_BF16 || dtype_out != GPV_BF16 || !k.vecA || !k.vecB || !k.ws_base) return -1;
   if (k.mask || k.rowscale || k.dthresh || k.accumulate || k.cg.dgrad || k.alpha != 1.0f || (k.act != 0 && k.act != GPV_ACT_RELU)) return -1;
-  if (k.N % 4 != 0 || k.ldc != k.N || (k.res && k.ldr != k.N) || !a16(k.C) || (k.res && !a16(k.res)) || (k.bias && !a16(k.bias))) return -1;
+  if (k.N % 4 != 0 || k.ldc != k.N || (k.res && k.ldr != k.N) || !al16(k.C) || (k.res && !al16(k.res)) || (k.bias && !al16(k.bias))) return -1;
   const int tiles = ((k.M + 63) / 64) * ((k.N + 63) / 64);
   const int kt_total = (k.K + BK - 1) / BK;
   if (tiles > 160 || kt_total < 32) return -1;
@@ -926,8 +890,6 @@ int launch_dtype(const GemmK& k, int batch, int dt_in, int dt_out, hipStream_t s
   return (int)hipErrorInvalidValue;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // Backward-data of a 1x1 stride-2 convolution (the downsample projections): only output pixels with even row AND column receive a
 // product; the other three quarters are dx = res * (mask > 0) (or 0).  The GEMM kernels take the first quarter (parity class 0 of
 // the class-major row order); this element-wise kernel streams the rest.  (Routed through the GEMM epilogue -- one dummy k-tile
@@ -980,7 +942,7 @@ extern "C" int gpv_gemm(const gpv_gemm_args* a, void* stream) {
   const int esz = a->dtype_in == GPV_F32 ? 4 : 2;
   const int64_t vecel = 16 / esz;  // elements per 16 B
   auto vec_ok = [&](const void* ptr, int64_t ld, int64_t bs, int layout, int extent_contig) {
-    bool ok = aligned16(ptr) && (ld % vecel == 0) && (a->batch == 1 || bs % vecel == 0);
+    bool ok = al16(ptr) && (ld % vecel == 0) && (a->batch == 1 || bs % vecel == 0);
     // 16-byte chunks: the contiguous extent must be a multiple of 8, or end inside the row pitch -- a reduction-major
     // operand's last chunk then only feeds outputs beyond M / N (discarded); a k-major operand's last chunk multiplies
     // masked rows of the other operand, so its padding must be finite (caller's promise: GPV_GEMM_KPAD_FINITE)
@@ -1066,12 +1028,12 @@ static int conv2d_impl(const gpv_conv_args* a, hipStream_t st, bool dry) {
     k.M = a->B * a->OH * a->OW; k.N = a->Cout; k.K = T * a->Cin;
     k.lda = 0; k.ldb = k.K; k.ldc = a->Cout;
     k.res = a->res; k.ldr = a->Cout; k.mask = a->relu_mask; k.ldm = a->Cout;
-    k.vecA = aligned16(a->x) && (a->Cs % vecel == 0 || (a->Cs * esz) % 8 == 0) ? 1 : 0;
+    k.vecA = al16(a->x) && (a->Cs % vecel == 0 || (a->Cs * esz) % 8 == 0) ? 1 : 0;
     // the stem reads 16-B runs at pixel granularity (Cs = 4 bf16 = 8 B): require 16-B aligned runs
     if ((a->Cs % vecel) != 0) k.vecA = ((a->SW * a->Cs) % vecel == 0 && (a->IW * a->Cs) % vecel == 0 && a->PW == 0) ? k.vecA : 0;
-    k.vecB = aligned16(a->w) && (k.K % 8 == 0) ? 1 : 0;
+    k.vecB = al16(a->w) && (k.K % 8 == 0) ? 1 : 0;
     if (a->mode == 0 && a->KH == 1 && a->KW == 1 && a->SH == 2 && a->SW == 2 && a->PH == 0 && a->PW == 0 &&
-        aligned16(a->x) && a->Cs % vecel == 0 && (int64_t)a->B * a->IH * a->IW * a->Cs * esz < 0x7ffffff0ll * 4ll) {
+        al16(a->x) && a->Cs % vecel == 0 && (int64_t)a->B * a->IH * a->IW * a->Cs * esz < 0x7ffffff0ll * 4ll) {
       // stride-2 pointwise projection (the downsample branches), forward: the streaming kernel reads every other pixel of every
       // other row (conv1x1_stream.hip); anything it does not take goes down the generic gather path below
       GemmK ks = k;
@@ -1094,7 +1056,7 @@ static int conv2d_impl(const gpv_conv_args* a, hipStream_t st, bool dry) {
         static const int64_t nt_min = (int64_t)tune_env("GPV_NT_MIN_MB", 200) << 20;
         k.nt_io = (int64_t)k.M * k.N * esz >= nt_min ? 1 : 0;
       }
-      k.vecA = aligned16(a->x) && (a->Cs % vecel == 0) && (int64_t)k.M * a->Cs * esz < 0x7ffffff0ll ? 1 : 0;
+      k.vecA = al16(a->x) && (a->Cs % vecel == 0) && (int64_t)k.M * a->Cs * esz < 0x7ffffff0ll ? 1 : 0;
       if (want_bits) {
         if (!k.vecA) return (int)hipErrorInvalidValue;
         k.out_bits = reinterpret_cast<uint32_t*>(a->y_mask_bits);
@@ -1119,8 +1081,8 @@ static int conv2d_impl(const gpv_conv_args* a, hipStream_t st, bool dry) {
     }
     static const bool s2_split = tune_env("GPV_S2_DGRAD_SPLIT", 1) != 0;
     if (s2_split && a->mode == 1 && k.cg.cm && a->KH == 1 && a->KW == 1 && a->PH == 0 && a->PW == 0 && a->dtype_in == GPV_BF16 &&
-        a->dtype_out == GPV_BF16 && a->Cout % 8 == 0 && aligned16(a->y) && (!a->res || aligned16(a->res)) &&
-        (!a->relu_mask || aligned16(a->relu_mask)) && k.vecA && k.vecB) {
+        a->dtype_out == GPV_BF16 && a->Cout % 8 == 0 && al16(a->y) && (!a->res || al16(a->res)) &&
+        (!a->relu_mask || al16(a->relu_mask)) && k.vecA && k.vecB) {
       // pointwise stride-2 backward-data: class 0 (even row, even column) through the GEMM kernels, the rest element-wise
       GemmK k0 = k;
       k0.M = k.cg.cls_rows;
@@ -1191,8 +1153,8 @@ static int conv2d_impl(const gpv_conv_args* a, hipStream_t st, bool dry) {
     k.split_k = split;
     if (split <= 1) { k.accumulate = 0; k.res = a->y; k.ldr = k.ldc; }
     k.ws_base = a->workspace; k.ws_bytes = a->workspace ? a->workspace_bytes : 0;
-    k.vecA = aligned16(a->w) && (a->Cout % vecel == 0) ? 1 : 0;
-    k.vecB = aligned16(a->x) && (a->Cs % vecel == 0) ? 1 : 0;
+    k.vecA = al16(a->w) && (a->Cout % vecel == 0) ? 1 : 0;
+    k.vecB = al16(a->x) && (a->Cs % vecel == 0) ? 1 : 0;
     // CONVT needs every N tile inside one tap: BN divides Cin (64 always does here; 128 when Cin % 128 == 0)
     {   // direct-to-LDS kernel (gemm_glds_tt.hip): 128-multiples of Cout / Cin with a workspace split reduction
       const int gw = glds_wgrad_try_launch(k, a->dtype_in, a->dtype_out, st);

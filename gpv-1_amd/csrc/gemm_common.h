@@ -48,6 +48,11 @@ __device__ __forceinline__ int conv_row_to_pixel(int m, const ConvGeom& g) {
 }
 
 
+// Register epilogue of the direct-to-LDS kernels (gemm_glds.hip, gemm_pipe.hip): the B rows (= output columns) are staged PERMUTED, LDS row r
+// holds output column depi_col_perm(r) -- common.h acc_chan's map, for any number of 32-column groups -- so that the accumulator tiles
+// 2 t, 2 t + 1 leave lane (row, g) with the 8 consecutive columns 32 t + 8 g .. + 7 of its row
+__device__ __forceinline__ int depi_col_perm(int r) { return (r & ~31) + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3); }
+
 // gemm_glds.hip: launches the 8-wave kernel when the problem qualifies.  Returns 0 = launched, -1 = not applicable
 // (caller falls back to the 4-wave kernel), > 0 = hipError_t.
 int glds_try_launch(const GemmK& k, int amode, int dtype_in, int dtype_out, int batch, hipStream_t st);

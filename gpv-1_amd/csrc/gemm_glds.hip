@@ -52,13 +52,8 @@ __device__ __forceinline__ void glds_body(const GemmK& p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform, but only provably so this way: LDS-DMA bases (M0) in SGPRs
   const int wm = wave / WN, wn = wave - wm * WN;
-  // XCD-aware tile order (see gemm.hip): contiguous tile range per XCD
-  int tile;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  // XCD-aware tile order (common.h xcd_contiguous): contiguous tile range per XCD
+  int tile = xcd_contiguous(blockIdx.x, gridDim.x);
   if constexpr (AMODE == OP_CONV) {
     if (p.cg.cm && p.cg.cls_rows % BM == 0 && p.M == 4 * p.cg.cls_rows) {
       // Stride-2 backward-data: row panel tm is parity class tm & 3 (next remap), so an XCD's contiguous tile range holds the four
@@ -67,8 +62,8 @@ __device__ __forceinline__ void glds_body(const GemmK& p) {
       // tiles first: class 3 (four taps), then 1 and 2 (two), then 0 (one); list scheduling of the same 1920 tiles on 512 slots:
       // makespan 80 -> 68 in units of k-tiles (ramp 8).
       const int nwg = gridDim.x, bid = blockIdx.x;
-      const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-      const int s0 = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, cnt = q + (xcd < r ? 1 : 0);
+      const int xcd = bid & 7, loc = bid >> 3;
+      const int s0 = xcd_contiguous(xcd, nwg), cnt = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);      // this XCD's tile range: it starts at the item of the XCD's first workgroup (bid = xcd, loc = 0)
       const int tN = p.tilesN, G = 4 * tN;
       auto below = [&](int x, int c) { const int m = x / G, u = x - m * G - c * tN; return m * tN + (u < 0 ? 0 : (u > tN ? tN : u)); };   // tiles < x of class c
       int left = loc, pick = 0, before = 0;
@@ -149,7 +144,7 @@ __device__ __forceinline__ void glds_body(const GemmK& p) {
   const bool bz = (AMODE == OP_CONV) && cm_empty;
   // Register epilogue (round 4): when the tile's columns are whole and every access is 16-byte aligned, the B rows
   // (= output columns) are staged PERMUTED -- LDS row L of a 32-row group holds column 8 (r / 4) + 4 jj + (r % 4), jj = L / 16 % 2,
-  // r = L % 16 (conv1x1_stream.hip's c1s_chan) -- so that the accumulator tiles 2t, 2t + 1 leave lane (row, g) with the 8 consecutive
+  // r = L % 16 (common.h acc_chan, depi_col_perm) -- so that the accumulator tiles 2t, 2t + 1 leave lane (row, g) with the 8 consecutive
   // columns 32 t + 8 g .. + 7 of its row: bias / residual / mask / output are plain 16-byte accesses in the accumulator layout, and
   // the fp32 LDS image with its four barriers per tile (16 us of serial ramp + store burst around the main loop) goes.
   const bool depi = p.depi && std::is_same<TOut, bf16>::value && p.N % BN == 0 && p.ldc % 8 == 0 &&
@@ -160,7 +155,7 @@ __device__ __forceinline__ void glds_body(const GemmK& p) {
 #pragma unroll
   for (int j = 0; j < BI; ++j) {
     const int r = wave * (BI * 8) + j * 8 + lrow;
-    const int rp = depi ? (r & ~31) + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3) : r;
+    const int rp = depi ? (r & ~31) + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3) : r;      // = depi_col_perm(r), written out: the call changes s_waitcnt / SGPR counts of the OP_CONV instances
     const int n = min(col0 + rp, p.N - 1);
     b_vo[j] = bz ? OOB : (n * (int)p.ldb + lchunk * 8) * 2;
   }
@@ -447,12 +442,7 @@ __global__ __launch_bounds__(256) void glds_halo_kernel(GemmK p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave - wm * WN;
-  int tile;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  int tile = xcd_contiguous(blockIdx.x, gridDim.x);
   const int tm = __builtin_amdgcn_readfirstlane(tile / p.tilesN);
   const int tn = tile - tm * p.tilesN;
   const int row0 = tm * BM, col0 = tn * BN;
@@ -478,7 +468,7 @@ __global__ __launch_bounds__(256) void glds_halo_kernel(GemmK p) {
 #pragma unroll
   for (int j = 0; j < BI; ++j) {
     const int r = wave * (BI * 8) + j * 8 + lrow;
-    const int rp = (r & ~31) + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3);      // permuted output columns (glds_body's register epilogue)
+    const int rp = depi_col_perm(r);      // permuted output columns (glds_body's register epilogue)
     b_vo[j] = ((col0 + rp) * (int)p.ldb + lchunk * 8) * 2;
   }
   auto bload = [&](const decltype(rsA)& rs, int voff, int soff, unsigned char* l) {
@@ -635,11 +625,10 @@ int launch_halo(const GemmK& k, hipStream_t st) {
 
 inline bool halo_ok(const GemmK& k, int dtype_out, int batch) {
   const ConvGeom& g = k.cg;
-  auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   return g_halo_mode != 0 && dtype_out == GPV_BF16 && batch == 1 && g.KH == 3 && g.KW == 3 && g.SH == 1 && g.SW == 1 && g.PH == 1 && g.PW == 1 &&
          !g.cm && g.OH == g.IH && g.OW == g.IW && g.IW <= 47 && g.Cin % GBK == 0 && k.N % 128 == 0 && k.K == 9 * g.Cin &&
-         k.M % (g.IH * g.IW) == 0 && k.ldc % 8 == 0 && a16(k.C) && (!k.res || (k.ldr % 8 == 0 && a16(k.res))) &&
-         (!k.mask || (k.ldm % 8 == 0 && a16(k.mask))) && (!k.bias || a16(k.bias)) && !k.dthresh && k.act != GPV_ACT_GELU;
+         k.M % (g.IH * g.IW) == 0 && k.ldc % 8 == 0 && al16(k.C) && (!k.res || (k.ldr % 8 == 0 && al16(k.res))) &&
+         (!k.mask || (k.ldm % 8 == 0 && al16(k.mask))) && (!k.bias || al16(k.bias)) && !k.dthresh && k.act != GPV_ACT_GELU;
 }
 
 // 1x1 stride-1 convolutions are plain GEMMs over the NHWC rows; their own kernel name keeps them attributable to the
@@ -687,8 +676,6 @@ int g_two_per_cu = tune_env("GPV_TWO_PER_CU", 1);
 int g_bm96_fill = tune_env("GPV_BM96", 1);       // 96-row tiles for <= 1024-row GEMMs (gemm_common.h two_per_cu_bm)
 namespace {
 int g_glds_mode = tune_env("GPV_GLDS", 1);   // gpv_set_option(GPV_OPT_GLDS, .)
-
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 }  // namespace
 

@@ -739,10 +739,9 @@ __device__ __forceinline__ void wg8h_core(const GemmK& p, int tile, int ksplit) 
 
 template <bool CONV>
 __device__ __forceinline__ void glds_tt_body(const GemmK& p) {
-  // (tile, split) plane, split-major, contiguous range per XCD (see gemm.hip): an XCD runs all tiles of one reduction slice
+  // (tile, split) plane, split-major, contiguous range per XCD (common.h xcd_contiguous; gemm.hip): an XCD runs all tiles of one reduction slice
   const int gx = gridDim.x, nwg = gx * (int)gridDim.y, bid = (int)blockIdx.x + gx * (int)blockIdx.y;
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+  const int v = xcd_contiguous(bid, nwg);
   const int ksplit = v / gx;
   glds_tt_core<CONV>(p, v - ksplit * gx, ksplit);
 }
@@ -800,8 +799,7 @@ static_assert(sizeof(WgGroupK) <= 4096, "kernel argument segment");
 template <int ABL>
 __device__ __forceinline__ void wgrad_group_body(const WgGroupK& g) {
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;     // contiguous unit range per XCD
+  const int v = xcd_contiguous(bid, nwg);     // contiguous unit range per XCD
   int pi = 0;
   while (pi + 1 < g.n && v >= g.prob[pi + 1].unit_start) ++pi;
   const WgProb& q = g.prob[pi];
@@ -821,8 +819,7 @@ __global__ __launch_bounds__(256) void glds_wgrad_group_kernel(WgGroupK g) { wgr
 // the problems whose Cout and Cin are multiples of 256 (layer3, layer4): the same units on 256 x 256 tiles, eight-phase core
 __global__ __launch_bounds__(512) void wg8_group_kernel(WgGroupK g) {
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;     // contiguous unit range per XCD
+  const int v = xcd_contiguous(bid, nwg);     // contiguous unit range per XCD
   int pi = 0;
   while (pi + 1 < g.n && v >= g.prob[pi + 1].unit_start) ++pi;
   const WgProb& q = g.prob[pi];
@@ -842,8 +839,7 @@ __global__ __launch_bounds__(512) void wg8_group_kernel(WgGroupK g) {
 // shape in bit 1 (0 = 128 x 256, 1 = 256 x 128)
 __global__ __launch_bounds__(512) void wg8h_group_kernel(WgGroupK g) {
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;     // contiguous unit range per XCD
+  const int v = xcd_contiguous(bid, nwg);     // contiguous unit range per XCD
   int pi = 0;
   while (pi + 1 < g.n && v >= g.prob[pi + 1].unit_start) ++pi;
   const WgProb& q = g.prob[pi];
@@ -963,8 +959,6 @@ int launch_tt(F fn, const GemmK& k, bool& attr_done, hipStream_t st) {
   return launch_splitk_reduce(p.ws, split, p.M, p.N, reinterpret_cast<float*>(p.C), p.ldc, st);
 }
 
-inline bool al16t(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 int g_wgrad_mode = tune_env("GPV_GLDS_WGRAD", 1);   // gpv_set_option(GPV_OPT_GLDS_WGRAD, .)
@@ -981,10 +975,10 @@ int glds_wgrad_try_launch(const GemmK& k, int dtype_in, int dtype_out, hipStream
   if (g_wgrad_mode == 0 || dtype_in != GPV_BF16 || dtype_out != GPV_F32) return -1;
   const ConvGeom& g = k.cg;
   if (k.M % TBM != 0 || g.Cin % TBN != 0 || k.N % TBN != 0) return -1;
-  if (g.Cs % 8 != 0 || k.lda % 8 != 0 || !al16t(k.A) || !al16t(k.B)) return -1;
+  if (g.Cs % 8 != 0 || k.lda % 8 != 0 || !al16(k.A) || !al16(k.B)) return -1;
   if (TBK / g.OW + 2 > g.OH || (int64_t)g.IH * g.IW * g.Cs * (k.K / (g.OH * g.OW)) >= (1ll << 30) ||
       (int64_t)k.K * k.lda >= (1ll << 30)) return -1;
-  if (!k.accumulate || k.ws_base == nullptr || !al16t(k.C) || k.ldc % 4 != 0) return -1;
+  if (!k.accumulate || k.ws_base == nullptr || !al16(k.C) || k.ldc % 4 != 0) return -1;
   static bool attr_done = false;
   return launch_tt(glds_wgrad_kernel, k, attr_done, st);
 }
@@ -999,8 +993,8 @@ int glds_tt_try_launch(const GemmK& k, int dtype_in, int dtype_out, int batch, h
   // once there is enough work to fill the chip -- 768x3072 / 3072x768 over 3200 rows 52 -> 35 us, 1536x768 36 -> 26 us,
   // 2048x256 over 9600 rows 33 -> 27 us -- and loses on the 4..36-tile gradients of short reductions (skinny_tt's territory)
   if (g_wgrad_mode == 1 && (int64_t)(k.M / TBM) * (k.N / TBN) * ((k.K + TBK - 1) / TBK) < 3000) return -1;
-  if (k.lda % 8 != 0 || k.ldb % 8 != 0 || !al16t(k.A) || !al16t(k.B)) return -1;
-  if (!k.accumulate || k.ws_base == nullptr || !al16t(k.C) || k.ldc % 4 != 0) return -1;
+  if (k.lda % 8 != 0 || k.ldb % 8 != 0 || !al16(k.A) || !al16(k.B)) return -1;
+  if (!k.accumulate || k.ws_base == nullptr || !al16(k.C) || k.ldc % 4 != 0) return -1;
   if (k.res || k.mask || k.bias || k.act || k.dthresh) return -1;
   static bool attr_done = false;
   return launch_tt(glds_tt_kernel, k, attr_done, st);
@@ -1025,7 +1019,7 @@ extern "C" int gpv_gemm_tt_group(const gpv_tt_problem* problems, int n, void* st
     for (int i = 0; i < g.n; ++i) {
       const gpv_tt_problem& q = problems[i0 + i];
       if (!q.A || !q.B || !q.C || q.M <= 0 || q.N <= 0 || q.K <= 0 || q.M % TBM != 0 || q.N % TBN != 0 || q.lda % 8 != 0 ||
-          q.ldb % 8 != 0 || q.ldc % 4 != 0 || !al16t(q.A) || !al16t(q.B) || !al16t(q.C) ||
+          q.ldb % 8 != 0 || q.ldc % 4 != 0 || !al16(q.A) || !al16(q.B) || !al16(q.C) ||
           (int64_t)q.K * q.lda >= (1ll << 30) || (int64_t)q.K * q.ldb >= (1ll << 30))
         return (int)hipErrorInvalidValue;
       g.prob[i] = q;
@@ -1074,7 +1068,7 @@ extern "C" int gpv_conv_wgrad_group(const gpv_conv_wgrad_problem* probs, int n, 
   static const int target_kt8 = [] { const int v = tune_env("GPV_WG8_KT", 150); return v < 8 ? 8 : v; }();
   auto eligible8 = [&](const gpv_conv_wgrad_problem& q) {
     const int64_t K64 = (int64_t)q.B * q.OH * q.OW;
-    return q.Cout % 256 == 0 && q.Cin % 256 == 0 && q.Cs % 8 == 0 && al16t(q.dy) && al16t(q.x) && al16t(q.dw) &&
+    return q.Cout % 256 == 0 && q.Cin % 256 == 0 && q.Cs % 8 == 0 && al16(q.dy) && al16(q.x) && al16(q.dw) &&
            TBK / q.OW + 2 <= q.OH && (int64_t)q.IH * q.IW * q.Cs * q.B < (1ll << 30) && K64 * q.Cout < (1ll << 30) && K64 >= 8 * TBK;
   };
   static bool attr8h_done = false;
@@ -1088,7 +1082,7 @@ extern "C" int gpv_conv_wgrad_group(const gpv_conv_wgrad_problem* probs, int n, 
   // a 128-wide side: Cout or Cin an odd multiple of 128 (or a 256-multiple problem the 256 x 256 launch did not take)
   auto eligible8h = [&](const gpv_conv_wgrad_problem& q) {
     const int64_t K64 = (int64_t)q.B * q.OH * q.OW;
-    return g_wg8h_mode != 0 && q.Cout % 128 == 0 && q.Cin % 128 == 0 && q.Cs % 8 == 0 && al16t(q.dy) && al16t(q.x) && al16t(q.dw) &&
+    return g_wg8h_mode != 0 && q.Cout % 128 == 0 && q.Cin % 128 == 0 && q.Cs % 8 == 0 && al16(q.dy) && al16(q.x) && al16(q.dw) &&
            TBK / q.OW + 2 <= q.OH && (int64_t)q.IH * q.IW * q.Cs * q.B < (1ll << 30) && K64 * q.Cout < (1ll << 30) && K64 >= 8 * TBK;
   };
   bool use8 = g_wg8_mode != 0;
@@ -1164,7 +1158,7 @@ extern "C" int gpv_conv_wgrad_group(const gpv_conv_wgrad_problem* probs, int n, 
     if (!q.x || !q.dy || !q.dw || q.B <= 0) return (int)hipErrorInvalidValue;
     const int M = q.Cout, N = q.KH * q.KW * q.Cin;
     const int64_t K64 = (int64_t)q.B * q.OH * q.OW;
-    const bool ok = M % TBM == 0 && q.Cin % TBN == 0 && q.Cs % 8 == 0 && al16t(q.dy) && al16t(q.x) && al16t(q.dw) &&
+    const bool ok = M % TBM == 0 && q.Cin % TBN == 0 && q.Cs % 8 == 0 && al16(q.dy) && al16(q.x) && al16(q.dw) &&
                     TBK / q.OW + 2 <= q.OH && (int64_t)q.IH * q.IW * q.Cs * q.B < (1ll << 30) && K64 * M < (1ll << 30) && K64 >= 8 * TBK;
     if (!ok) {                                       // a shape the direct-to-LDS kernel does not take: its own launch
       gpv_conv_args a{};
@@ -1296,7 +1290,7 @@ extern "C" int gpv_gemm_tt_group_ws(const gpv_tt_problem* problems, int n, void*
   for (int i = 0; i < n; ++i) {
     const gpv_tt_problem& q = problems[i];
     const bool big = g_w8l_mode != 0 && q.A && q.B && q.C && q.M > 0 && q.N > 0 && q.M % 256 == 0 && q.N % 256 == 0 && q.K >= 2 * TBK && (int64_t)q.M * q.N < (1ll << 30) &&
-                     q.lda % 8 == 0 && q.ldb % 8 == 0 && q.ldc % 4 == 0 && al16t(q.A) && al16t(q.B) && al16t(q.C) &&
+                     q.lda % 8 == 0 && q.ldb % 8 == 0 && q.ldc % 4 == 0 && al16(q.A) && al16(q.B) && al16(q.C) &&
                      (int64_t)q.K * q.lda < (1ll << 30) && (int64_t)q.K * q.ldb < (1ll << 30);
     if (!big) {
       if (n_rest == GPV_TT_GROUP_MAX) { const int e = flush_rest(); if (e) return e; }

@@ -79,12 +79,7 @@ __device__ __forceinline__ void pipe_body(const GemmK& p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave - wm * WN;
-  int tile;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  int tile = xcd_contiguous(blockIdx.x, gridDim.x);
   int tm = __builtin_amdgcn_readfirstlane(tile / p.tilesN);
   const int tn = tile - tm * p.tilesN;
   if constexpr (AMODE == OP_CONV) {
@@ -151,7 +146,7 @@ __device__ __forceinline__ void pipe_body(const GemmK& p) {
 #pragma unroll
   for (int j = 0; j < BI; ++j) {
     const int r = (j * NW + wave) * 8 + lrow;
-    const int rp = depi ? (r & ~31) + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3) : r;
+    const int rp = depi ? (r & ~31) + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3) : r;      // = depi_col_perm(r), written out: the call changes s_waitcnt / SGPR counts of the OP_CONV instances
     const int n = min(col0 + rp, p.N - 1);
     b_vo[j] = bz ? OOB : (n * (int)p.ldb + lchunk * 8) * 2;
   }
@@ -481,8 +476,6 @@ int launch_cfg_idx(int idx, const GemmK& k, int batch, hipStream_t st) {
 
 int g_pipe_small = tune_env("GPV_PIPE_SMALL", 1);   // the small-M configurations (64 x 64 / 32 x 64, 6 / 8 stages)
 int g_pipe_mode = tune_env("GPV_PIPE", 1);   // 0 off, 1 heuristic, 100+i: force configuration i wherever legal
-
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // rounds of 256 CUs a configuration needs, weighted by the tile's MFMA work; ties go to the larger tile (operand reuse)
 int pick_cfg(const GemmK& k, int batch) {

@@ -64,7 +64,6 @@ __global__ __launch_bounds__(256) void skinny_kernel(GemmK p) {
   // operands through buffer loads: per-thread 32-bit byte offsets fixed for the tile, the k-step offset in the scalar soffset,
   // an out-of-range offset (reduction tail, columns beyond N) = hardware zeros -- no 64-bit address add, no safe-address
   // select and no zeroing selects per load (this loader issued ~64 VALU instructions per 16 MFMAs)
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   constexpr int OOB = 0x7ffffff0;
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(A), (short)0, OOB, 0x00020000);
   const auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(B), (short)0, OOB, 0x00020000);
@@ -296,7 +295,6 @@ __global__ __launch_bounds__(256) void skinny_tt_kernel(GemmK p) {
   const int tc = tid & 7, tr = tid >> 3;
   const bool a_ok = row0 + tc * 8 < p.M, b_ok = col0 + tc * 8 < p.N;      // M % 8 == 0, N % 8 == 0 (host)
   // buffer loads (see skinny_kernel): fixed per-thread offsets, the k-step offset in soffset, out-of-range = zeros
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   constexpr int OOB = 0x7ffffff0;
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(A), (short)0, OOB, 0x00020000);
   const auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(B), (short)0, OOB, 0x00020000);
@@ -400,14 +398,12 @@ __global__ __launch_bounds__(256) void skinny_tt_kernel(GemmK p) {
   }
 }
 
-inline bool al16s(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 // returns 0 = launched, -1 = not applicable, > 0 = hipError_t.  b_trans: B is reduction-major (GPV_TRANS): dX = dY W.
 int skinny_try_launch(const GemmK& k, int b_trans, int dtype_in, int dtype_out, int batch, hipStream_t st) {
   if (g_skinny_mode == 0 || dtype_in != GPV_BF16 || batch != 1 || k.accumulate || k.split_k > 1) return -1;
-  if (k.K % 8 != 0 || k.lda % 8 != 0 || k.ldb % 8 != 0 || !al16s(k.A) || !al16s(k.B)) return -1;
+  if (k.K % 8 != 0 || k.lda % 8 != 0 || k.ldb % 8 != 0 || !al16(k.A) || !al16(k.B)) return -1;
   if (b_trans && k.N % 8 != 0) return -1;
   {   // 32-bit byte offsets into each operand
     const int64_t lim = 0x7ffffff0ll / 2;
@@ -429,7 +425,7 @@ int skinny_try_launch(const GemmK& k, int b_trans, int dtype_in, int dtype_out, 
 int skinny_tt_try_launch(const GemmK& k, int dtype_in, int dtype_out, int batch, hipStream_t st) {
   if (g_skinny_mode == 0 || dtype_in != GPV_BF16 || dtype_out != GPV_F32 || batch != 1 || !k.accumulate) return -1;
   if (k.M % 8 != 0 || k.N % 8 != 0 || k.lda % 8 != 0 || k.ldb % 8 != 0 || k.ldc % 4 != 0) return -1;
-  if (!al16s(k.A) || !al16s(k.B) || !al16s(k.C) || k.res || k.mask || k.bias || k.act || k.dthresh) return -1;
+  if (!al16(k.A) || !al16(k.B) || !al16(k.C) || k.res || k.mask || k.bias || k.act || k.dthresh) return -1;
   if ((int64_t)k.K * k.lda >= 0x7ffffff0ll / 2 || (int64_t)k.K * k.ldb >= 0x7ffffff0ll / 2) return -1;   // 32-bit byte offsets
   const int64_t tiles = (int64_t)((k.M + SBM - 1) / SBM) * ((k.N + SBN - 1) / SBN);
   const int nk = (k.K + SBK - 1) / SBK;

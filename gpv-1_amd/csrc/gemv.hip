@@ -86,8 +86,6 @@ int launch_mr(const GemmK& k, hipStream_t st) {
   return launch_nw<TI, TO, 8>(k, st);
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // one workgroup of 1024 threads per row: the index of the largest x[r, v] + addend[v]; equal values -> the lowest index; NaNs
 // never win.  16-byte pieces of the row when its base and pitch allow (V = 10000 bf16: 1250 pieces, 1.2 per thread).
 template <typename T>

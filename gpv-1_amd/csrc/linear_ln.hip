@@ -18,7 +18,6 @@
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct LinLnK {
   const bf16* a; const bf16* w; const float* bias; const bf16* x; const float* gamma; const float* beta;
@@ -29,12 +28,7 @@ struct LinLnK {
 constexpr int LK = 256, LN_ = 256, LKC = LK / 32, LNT = LN_ / 16, LNG = LN_ / 32, LROW = LK * 2;     // LDS row = 512 bytes, no padding: XOR swizzle
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-// LDS row L holds output channel chan(L): MFMA tile j = L / 16, row r = L % 16 -> channel 32 (j / 2) + 8 (r / 4) + 4 (j & 1) + (r % 4)
-// (conv1x1_stream.hip's c1s_chan): tiles 2 t, 2 t + 1 leave lane (row, g) with the 8 consecutive channels 32 t + 8 g .. + 7
-__device__ __forceinline__ int lin_chan(int L) {
-  const int j = L >> 4, r = L & 15;
-  return (j >> 1) * 32 + (r >> 2) * 8 + (j & 1) * 4 + (r & 3);
-}
+// LDS row L holds output channel acc_chan(L) (common.h): tiles 2 t, 2 t + 1 leave lane (row, g) with the 8 consecutive channels 32 t + 8 g .. + 7
 
 template <bool FULLM, bool DROP, bool POS>
 __device__ __forceinline__ void linear_ln_tiles(const LinLnK& p, unsigned char* smem_raw, int tile, int ntile, int nw, bf16x8 (&an)[LKC]) {
@@ -177,7 +171,7 @@ __global__ __launch_bounds__(256) void linear_ln_kernel(LinLnK p) {
     for (int i = 0; i < 32; ++i) {                       // 128 instructions of 1 KB, 32 per wave
       const int inst = wv * 32 + i;
       const int L = inst * 2 + (lane >> 5), sl = lane & 31;
-      const int voff = (lin_chan(L) * LK + ((sl ^ (L & 15)) * 8)) * 2;
+      const int voff = (acc_chan(L) * LK + ((sl ^ (L & 15)) * 8)) * 2;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_void_t*)(smem_raw + inst * 1024), 16, voff, 0, 0, 0);
     }
   }
@@ -198,8 +192,6 @@ __global__ __launch_bounds__(256) void linear_ln_kernel(LinLnK p) {
 #undef GO
 }
 
-inline bool al16l(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int gpv_linear_layernorm_fwd(const void* a, const void* w, const float* bias, const void* x, const float* gamma,
@@ -208,8 +200,8 @@ extern "C" int gpv_linear_layernorm_fwd(const void* a, const void* w, const floa
   if (!a || !w || !x || !s || !y || !mean || !rstd || rows <= 0 || rows > (1 << 23)) return (int)hipErrorInvalidValue;
   if (K != LK || N != LN_) return (int)hipErrorInvalidValue;                      // the DETR width only
   if ((gamma == nullptr) != (beta == nullptr) || (pos == nullptr) != (y2 == nullptr) || (pos && pos_rows <= 0)) return (int)hipErrorInvalidValue;
-  if (!al16l(a) || !al16l(w) || !al16l(x) || !al16l(s) || !al16l(y) || (pos && (!al16l(pos) || !al16l(y2))) || (gamma && (!al16l(gamma) || !al16l(beta))) ||
-      (bias && !al16l(bias)))
+  if (!al16(a) || !al16(w) || !al16(x) || !al16(s) || !al16(y) || (pos && (!al16(pos) || !al16(y2))) || (gamma && (!al16(gamma) || !al16(beta))) ||
+      (bias && !al16(bias)))
     return (int)hipErrorInvalidValue;
   LinLnK p{};
   p.a = reinterpret_cast<const bf16*>(a); p.w = reinterpret_cast<const bf16*>(w); p.bias = bias; p.x = reinterpret_cast<const bf16*>(x);

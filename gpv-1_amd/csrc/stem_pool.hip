@@ -21,7 +21,6 @@
 namespace gpvk {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
