@@ -8,9 +8,30 @@
 
   * CocoDetection / RefCocop      (evaluators.py:210-365)  one AP per sample from the boxes file, mAP = np.mean(APs)
 
-Captioning (Bleu / Cider) calls third-party scorers the reference keeps under third_party/ (empty in the checkout: un-vendored); its
-input is the prediction file gpv1_amd.compute_predictions writes in the reference's layout, so the reference's evaluator consumes
-it as it is.
+  * CocoCaptioning.evaluate       (evaluators.py:130-207)  Bleu1..4 and CIDEr-D of the lower-cased prediction against every caption of
+                                                            the same image among the given samples
+
+Captioning: the reference calls pycocoevalcap's Bleu and Cider (third_party/, empty in the checkout: un-vendored), so the rule is
+restated here from the published algorithm (bleu_scorer.py, cider_scorer.py) -- ``caption_scores_host`` -- and is the specification
+of the device scorer (csrc/caption_score.hip).  hyps[i]: a list of words, refs[i]: a non-empty list of such lists, N = len(hyps):
+  * n-grams: every contiguous window of 1..4 words of a caption, counted with multiplicity;
+  * Bleu (option 'closest', corpus level), per entry: testlen = len(hyp); reflen = the reference length closest to testlen, the
+    shorter one on a tie (min((abs(l - testlen), l) for l in reflens)[1]); guess[k] = max(0, testlen - k), k = 0..3; correct[k] =
+    sum over the hypothesis' distinct (k+1)-grams of min(count in hyp, max over refs of the count in that ref).  The totals over the
+    entries are integers; with b = 1, for k = 0..3: b *= (correct[k] + 1e-15) / (guess[k] + 1e-9), Bleu_{k+1} = b ** (1 / (k + 1));
+    ratio = (testlen + 1e-15) / (reflen + 1e-9); if ratio < 1 every Bleu_k is multiplied by exp(1 - 1 / ratio);
+  * CIDEr-D (n = 4, sigma = 6): df[g] = the number of entries in which n-gram g occurs in at least one reference; the weight table
+    w[d] = log(N) - log(max(1, d)), d = 0..N, float64, computed ONCE with numpy (``caption_tables``) and read by the host rule and by
+    the kernel alike -- neither recomputes a logarithm; the vector of a caption at order n is tf(g) * w[df[g]] over its distinct
+    n-grams (an n-gram no reference holds has df 0), its norm the square root of the sum of squares; the caption's ``length`` is the
+    number of its BIGRAM occurrences, max(0, len - 1) (a quirk of the original, kept); for a hypothesis h and a reference r,
+    val[n] = sum over h's distinct n-grams of min(vec_h[g], vec_r[g]) * vec_r[g], divided by norm_h[n] * norm_r[n] only if both are
+    non-zero, times pen[|length_h - length_r|], pen[d] = e ** (-(d * d) / (2 * 36)), again one shared float64 table; the entry scores
+    10 * (sum over n of the sum over refs of val[n]) / 4 / len(refs); Cider = the float64 mean of the entry scores.  With N = 1 every
+    weight is 0 and so is the score.
+NOT reproduced: the Stanford PTB tokenizer (a Java program).  ``simple_caption_tokenize`` lower-cases, splits on whitespace and drops
+the punctuation of pycocoevalcap's removal list; it does not split clitics (n't, 's), so a figure that depends on that splitting --
+any published COCO caption score -- is not reproduced to the digit.  Pass ``tokenize=`` to use the real tool.
 
 Detection / referring-expression AP: the reference hands every sample to third_party/detection_metrics, which is un-vendored too, so
 the per-sample rule is restated here (``det_ap_host``) and is the specification of the device scorer (csrc/det_ap.hip):
@@ -29,6 +50,8 @@ the (W, H) image and measures widths, heights and areas with ``+ 1`` -- so its A
 
 Pinned by tests/golden/evaluators.json, produced by the reference's own classes (tools/gen_golden_evaluators.py); the IoU by
 tests/golden/detection_iou.json, produced by the reference's utils/bbox_utils.py compute_iou (tools/gen_golden_detection.py)."""
+import math
+import re
 from collections import Counter
 
 import numpy as np
@@ -235,3 +258,162 @@ class RefCocop(CocoDetection):
 
     def __init__(self, samples, predictions, boxes, task='RefCocop'):
         super().__init__(samples, predictions, boxes, task)
+
+
+CAP_ORDERS = 4
+CAP_SIGMA = 6.0
+CAP_KEYS = ('Bleu1', 'Bleu2', 'Bleu3', 'Bleu4', 'Cider')
+# pycocoevalcap's PUNCTUATIONS (ptbtokenizer.py), lower-cased: tokens the PTB tokenizer's output is filtered by
+CAP_PUNCTUATION = ("''", "'", '``', '`', '-lrb-', '-rrb-', '-lcb-', '-rcb-', '.', '?', '!', ',', ':', '-', '--', '...', ';')
+_CAP_BRACKETS = re.compile(r'-(?:lrb|rrb|lcb|rcb)-')
+_CAP_ANYWHERE = re.compile(r"\.\.\.|--|``|''|[.?!,:;]")
+
+
+def simple_caption_tokenize(text):
+    """str -> list of words: lower-cased, split on whitespace, the marks of CAP_PUNCTUATION split off the words and dropped.
+    `. ? ! , : ; ... -- `` ''` and the bracket names split a word wherever they stand; `'`, '`' and `-` are taken off a word's ends
+    only, so "don't" and "well-known" stay one word each.
+    NOT reproduced: the Stanford PTB tokenizer the reference runs -- no clitic splitting ("don't" -> "do n't", "dog's" -> "dog 's"),
+    no number handling ("3.5" becomes "3", "5" here) -- and so any figure that depends on it."""
+    words = []
+    for tok in str(text).lower().split():
+        for part in _CAP_ANYWHERE.sub(' ', _CAP_BRACKETS.sub(' ', tok)).split():
+            part = part.strip("'`-")
+            if part:
+                words.append(part)
+    return words
+
+
+def caption_tables(n_entries, max_len):
+    """the two float64 tables both the host rule and the kernel read: weight[d] = log(N) - log(max(1, d)) for d = 0..N, and
+    pen[d] = e ** (-(d * d) / (2 * sigma^2)) for d = 0..max(1, max_len) - 1 (d: a difference of bigram counts)"""
+    d = np.arange(n_entries + 1, dtype=np.float64)
+    weight = np.log(np.float64(max(n_entries, 1))) - np.log(np.maximum(1.0, d))
+    k = np.arange(max(1, int(max_len)), dtype=np.float64)
+    pen = np.e ** (-(k * k) / (2 * CAP_SIGMA ** 2))
+    return weight, pen
+
+
+def _ngram_counts(words):
+    """{n-gram tuple: occurrences}, orders 1..4"""
+    c = Counter()
+    for n in range(1, CAP_ORDERS + 1):
+        for p in range(len(words) - n + 1):
+            c[tuple(words[p:p + n])] += 1
+    return c
+
+
+def bleu_from_totals(testlen, reflen, guess, correct):
+    """corpus Bleu1..4 from the integer totals (module docstring) -> list of 4 floats"""
+    bleus, b = [], 1.0
+    for k in range(CAP_ORDERS):
+        b *= (float(correct[k]) + 1e-15) / (float(guess[k]) + 1e-9)
+        bleus.append(b ** (1.0 / (k + 1)))
+    ratio = (float(testlen) + 1e-15) / (float(reflen) + 1e-9)
+    if ratio < 1:
+        factor = math.exp(1 - 1 / ratio)                               # underflows to 0.0 for an empty hypothesis corpus
+        bleus = [x * factor for x in bleus]
+    return bleus
+
+
+def caption_result(testlen, reflen, guess, correct, cider):
+    """the finish both paths share: per-entry integers [N], [N], [N,4], [N,4] and per-entry CIDEr [N] float64 -> the result dict
+    (int64 sums, float64 mean)"""
+    testlen, reflen = np.asarray(testlen, dtype=np.int64).reshape(-1), np.asarray(reflen, dtype=np.int64).reshape(-1)
+    guess, correct = np.asarray(guess, dtype=np.int64).reshape(-1, CAP_ORDERS), np.asarray(correct, dtype=np.int64).reshape(-1, CAP_ORDERS)
+    cider = np.asarray(cider, dtype=np.float64).reshape(-1)
+    totals = {'testlen': int(testlen.sum()), 'reflen': int(reflen.sum()), 'guess': [int(v) for v in guess.sum(0)],
+              'correct': [int(v) for v in correct.sum(0)]}
+    if len(cider) == 0:
+        bleus, mean = [0.0] * CAP_ORDERS, 0.0
+    else:
+        bleus, mean = bleu_from_totals(totals['testlen'], totals['reflen'], totals['guess'], totals['correct']), float(np.mean(cider))
+    out = {f'Bleu{k + 1}': bleus[k] for k in range(CAP_ORDERS)}
+    out.update(Cider=mean, cider_entries=cider, bleu_totals=totals,
+               bleu_entries={'testlen': testlen, 'reflen': reflen, 'guess': guess, 'correct': correct})
+    return out
+
+
+def caption_scores_host(hyps, refs):
+    """the rule of the module docstring, as pycocoevalcap states it (dicts of n-gram tuples).  hyps[i]: list of words, refs[i]:
+    non-empty list of lists of words -> {'Bleu1'..'Bleu4', 'Cider', 'cider_entries': float64 [N], 'bleu_totals': {'testlen',
+    'reflen', 'guess' [4], 'correct' [4]} ints, 'bleu_entries': the same per entry, 'df': {n-gram tuple: document frequency}}"""
+    N = len(hyps)
+    if len(refs) != N or any(len(r) == 0 for r in refs):
+        raise ValueError('caption_scores_host: every entry needs a hypothesis and at least one reference')
+    hyp_c = [_ngram_counts(h) for h in hyps]
+    ref_c = [[_ngram_counts(r) for r in rs] for rs in refs]
+    df = Counter()
+    for rcs in ref_c:
+        for g in set().union(*rcs):
+            df[g] += 1
+    max_len = max([len(h) for h in hyps] + [len(r) for rs in refs for r in rs] + [1])
+    weight, pen = caption_tables(N, max_len)
+
+    def vector(counts):
+        vec = [{} for _ in range(CAP_ORDERS)]
+        for g, tf in counts.items():
+            vec[len(g) - 1][g] = float(tf) * weight[df.get(g, 0)]
+        return vec, [math.sqrt(sum(v * v for v in o.values())) for o in vec]
+
+    testlen, reflen, guess, correct, cider = [], [], [], [], []
+    for i in range(N):
+        tl = len(hyps[i])
+        testlen.append(tl)
+        reflen.append(min((abs(len(r) - tl), len(r)) for r in refs[i])[1])
+        guess.append([max(0, tl - k) for k in range(CAP_ORDERS)])
+        cor = [0] * CAP_ORDERS
+        for g, c in hyp_c[i].items():
+            cor[len(g) - 1] += min(c, max(rc.get(g, 0) for rc in ref_c[i]))
+        correct.append(cor)
+        vec_h, norm_h = vector(hyp_c[i])
+        length_h = max(0, tl - 1)
+        total = [0.0] * CAP_ORDERS
+        for r, rc in zip(refs[i], ref_c[i]):
+            vec_r, norm_r = vector(rc)
+            p = pen[abs(length_h - max(0, len(r) - 1))]
+            for n in range(CAP_ORDERS):
+                val = sum(min(v, vec_r[n].get(g, 0.0)) * vec_r[n].get(g, 0.0) for g, v in vec_h[n].items())
+                if norm_h[n] != 0 and norm_r[n] != 0:
+                    val /= norm_h[n] * norm_r[n]
+                total[n] += val * p
+        cider.append(10.0 * sum(total) / CAP_ORDERS / len(refs[i]))
+    out = caption_result(testlen, reflen, guess, correct, cider)
+    out['df'] = dict(df)
+    return out
+
+
+class CocoCaptioning(CocoEval):
+    """evaluators.py:130-207: an entry is a cap_id with a prediction; its references are the lower-cased answers of every GIVEN sample
+    of the same (image.subset, image.image_id); the hypothesis is the lower-cased prediction.  tokenize: str -> words
+    (simple_caption_tokenize; the reference runs the PTB tokenizer); scores: (hyps, refs) -> the dict of caption_scores_host (the
+    device scorer of gpv1_amd.caption_scorer has the same signature)."""
+
+    def __init__(self, samples, predictions, boxes=None, task='CocoCaptioning', tokenize=None, scores=None):
+        super().__init__(samples, predictions, boxes, task)
+        self.tokenize = simple_caption_tokenize if tokenize is None else tokenize
+        self.scores = caption_scores_host if scores is None else scores
+        self.subset_imgid2gtcaps = {}
+        for s in samples:
+            self.subset_imgid2gtcaps.setdefault(self._image_key(s), []).append(s['answer'].lower())
+
+    @staticmethod
+    def _image_key(sample):
+        return f"{sample['image'].get('subset')}_{str(sample['image']['image_id']).zfill(12)}"
+
+    def evaluate(self, novelty='everything'):
+        picked, absent = self._selected(novelty)
+        cache = {}
+        hyps, refs = [], []
+        for k, sample in picked:
+            key = self._image_key(sample)
+            if key not in cache:
+                cache[key] = [self.tokenize(c) for c in self.subset_imgid2gtcaps[key]]
+            hyps.append(self.tokenize(self.predictions[k]['answer'].lower()))
+            refs.append(cache[key])
+        if hyps:
+            full = self.scores(hyps, refs)
+            scores = {k: full[k] for k in CAP_KEYS}
+        else:
+            scores = {k: 0 for k in CAP_KEYS}
+        return {'absent': absent, 'total': len(hyps), 'scores': scores}

@@ -16,8 +16,8 @@ sample by sample in Python.  Here the per-sample AP is one launch per batch on t
 scorer, and the dataset ends in one device-to-host copy and one float64 ``np.mean``.  ``host=True`` is the comparison path:
 ``inference.decode_outputs`` plus the ``evaluators`` classes, as the reference does it.
 
-Captioning: Bleu, CIDEr and the PTB tokenizer are un-vendored; ``cap_metrics`` returns the predictions and calls a scorer only if
-the caller supplies one.
+Captioning: ``cap_metrics`` returns the predictions and calls a scorer only if the caller supplies one;
+``caption_scorer.CaptionScorer`` is that scorer (Bleu / CIDEr-D restated, on the device; the PTB tokenizer is not reproduced).
 """
 import numpy as np
 import torch

@@ -20,10 +20,11 @@ What is reproduced -- everything between the data loader and the checkpoint file
     ``model_selection_metric = vqa_acc + cider + det_map + cls_acc`` on ``val`` and writes ``ckpt_dir/model.pth`` only when it
     exceeds the best so far; the periodic and epoch-end saves go to ``model_last.pth`` (carrying the best metric so far), a
     resume takes ``best_metric`` from the checkpoint (:283); the other ranks wait at a barrier.  Detection mAP is scored on
-    the device (csrc/det_ap.hip).  ``cider`` is 0 unless the dataset carries a caption ``scorer`` (Bleu / CIDEr are
-    un-vendored); the reference leaves ``refcocop`` out of the sum, so its mAP is logged only.  Evaluation leaves the
-    training state alone: ``model.eval()`` / ``no_grad`` / ``model.train()``, no RNG draw, the captured training graphs are
-    replayed afterwards, not recaptured.
+    the device (csrc/det_ap.hip).  ``cider`` comes from the dataset's caption ``scorer`` if it carries one, else from a
+    ``caption_scorer.CaptionScorer`` when ``training.caption_scorer`` is ``'device'`` (csrc/caption_score.hip) or ``'host'``, else
+    it is 0 and the log says so (the reference's pycocoevalcap is un-vendored); the reference leaves ``refcocop`` out of the
+    sum, so its mAP is logged only.  Evaluation leaves the training state alone: ``model.eval()`` / ``no_grad`` /
+    ``model.train()``, no RNG draw, the captured training graphs are replayed afterwards, not recaptured.
 Out of scope: dataset ETL, TensorBoard, HTML.  Without ``eval_datasets`` this driver checkpoints every
 ``training.ckpt_step`` steps and at every epoch end into ``model.pth``.
 The dataset is any sequence of ``(image[3,H,W] fp32 normalised, query str | (ids, mask), target dict)``;
@@ -124,9 +125,16 @@ def _eval_cls(model, batches_, ds, limit):
     return metrics.cls_metrics(model, batches_, ds.samples, limit, synonyms=getattr(ds, 'synonyms', None))
 
 
-def _eval_cap(model, batches_, ds, limit):
+def _eval_cap(model, batches_, ds, limit, mode=None):
+    """mode: cfg.training.caption_scorer -- 'device' | 'host' builds a caption_scorer.CaptionScorer when the dataset carries no scorer"""
     from . import metrics
-    scores, _ = metrics.cap_metrics(model, batches_, ds.samples, limit, scorer=getattr(ds, 'scorer', None))
+    scorer = getattr(ds, 'scorer', None)
+    if scorer is None and mode is not None:
+        if mode not in ('device', 'host'):
+            raise ValueError(f"training.caption_scorer must be 'device' or 'host', got {mode!r}")
+        from .caption_scorer import CaptionScorer
+        scorer = CaptionScorer(device=None if mode == 'host' else metrics._device(model), host=mode == 'host')
+    scores, _ = metrics.cap_metrics(model, batches_, ds.samples, limit, scorer=scorer)
     return scores
 
 
@@ -162,7 +170,10 @@ def evaluate_subset(model, datasets, subset, cfg, epoch, device, log=print, said
                 if fn is None:
                     log(f'Eval not implemented for {name}')
                     continue
-                out = fn(model, eval_batches(ds, batch_size, device), ds, limits.get(name, None))
+                if fn is _eval_cap:
+                    out = fn(model, eval_batches(ds, batch_size, device), ds, limits.get(name, None), tr_cfg.get('caption_scorer', None))
+                else:
+                    out = fn(model, eval_batches(ds, batch_size, device), ds, limits.get(name, None))
                 if name == 'coco_vqa':
                     vqa_acc = out
                     log(f'Dataset: {name} | Subset: {subset} | Epoch: {epoch} | Acc: {out}')

@@ -7,7 +7,14 @@
 The dataset (images on the device, tokenised queries, 1..10 ground-truth boxes per sample) is built once; a pass is the whole
 det_metrics call -- greedy forward per batch, scoring, the final copy -- ending in a device synchronise.  Two warm-up passes per
 path (graph capture, kernel attributes), then the two paths ALTERNATE for `repeats` timed passes each; the spread reported is
-(max - min) / median of a path's passes.  Forward time alone (the same loop without scoring) is printed for scale."""
+(max - min) / median of a path's passes.  Forward time alone (the same loop without scoring) is printed for scale.
+
+Caption pass:  python tools/bench_eval.py --captions [--repeats 5] [--out profiles/r09_cap_eval.txt]
+5000 synthetic entries, five references of 8..15 words each, hypotheses of 6..14 words, a Zipf vocabulary of 3000 words (the input the
+plain-Python scorers were timed on).  A pass is caption_scorer.CaptionScorer.scores(hyps, refs) on tokenised captions: for the device
+path the word -> id encoding on the host, the one upload, the launches and the one copy back; for host=True the host rule.  The two
+paths alternate; the device path's own share (hip_cap.caption_scores between two events) and the greedy forward of the detection
+pass above (images/s, scaled to 5000 images) are printed beside them."""
 import argparse
 import csv
 import glob
@@ -82,6 +89,77 @@ def stats(trace_dir):
             'min %.2f us, max %.2f us' % (B, len(us), sum(us) / len(us), us[len(us) // 2], us[0], us[-1]))
 
 
+def caption_entries(n=5000, refs_per_entry=5, vocab=3000, seed=0):
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    p = 1.0 / np.arange(1, vocab + 1)
+    p /= p.sum()
+    words = np.asarray(['w%d' % i for i in range(vocab)])
+    draw = lambda lo, hi: words[rs.choice(vocab, size=rs.randint(lo, hi + 1), p=p)].tolist()
+    return [draw(6, 14) for _ in range(n)], [[draw(8, 15) for _ in range(refs_per_entry)] for _ in range(n)]
+
+
+def caption_pass(args, dev):
+    import numpy as np
+    import torch
+    from gpv1_amd import evaluators, hip_cap
+    from gpv1_amd.caption_scorer import CaptionScorer, encode_captions
+    hyps, refs = caption_entries()
+    paths = {False: CaptionScorer(device=dev), True: CaptionScorer(host=True)}
+
+    def one(host):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = paths[host].scores(hyps, refs)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+    one(False)
+    one(False)
+    t, res = {False: [], True: []}, {}
+    for _ in range(args.repeats):
+        for host in (False, True):
+            dt, res[host] = one(host)
+            t[host].append(dt)
+    # the device path's parts: the host-side encoding, and the launches alone between two events (arrays already on the device)
+    t0 = time.perf_counter()
+    arrays = encode_captions(hyps, refs)
+    t_enc = time.perf_counter() - t0
+    N, LH = arrays[0].shape
+    LR = arrays[2].shape[2]
+    tables = evaluators.caption_tables(N, max(LH, LR))
+    d = [torch.from_numpy(a).to(dev) for a in arrays[:5] + tables]
+    ev = []
+    for _ in range(args.repeats + 2):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        hip_cap.caption_scores(*d, occurrences=arrays[5])
+        b.record()
+        torch.cuda.synchronize()
+        ev.append(a.elapsed_time(b))
+    ev = ev[2:]
+    med = lambda v: sorted(v)[len(v) // 2]
+    fmt = lambda v: 'median %.1f ms   passes ms: %s   spread (max-min)/median %.1f%%' % (
+        med(v) * 1e3, ' '.join('%.1f' % (x * 1e3) for x in v), 100 * (max(v) - min(v)) / med(v))
+    worst = float(np.abs(res[False]['cider_entries'] - res[True]['cider_entries']).max())
+    lines = ['caption scoring, %d entries x 5 references of 8..15 words, hypotheses of 6..14 words, Zipf vocabulary of 3000 words, %d alternating passes per path'
+             % (N, args.repeats),
+             '  %-58s %s' % ('device scorer (encode + upload + csrc/caption_score.hip + copy)', fmt(t[False])),
+             '  %-58s %s' % ('host=True (evaluators.caption_scores_host)', fmt(t[True])),
+             '  device path, parts: word -> id encoding on the host %.1f ms; memsets + two kernels between events: median %.3f ms (%s), table of %d slots'
+             % (t_enc * 1e3, med(ev), ' '.join('%.3f' % x for x in ev), hip_cap.table_capacity(arrays[5])),
+             '  host / device: %.1fx   Cider device %.12f host %.12f   Bleu4 device %.12f host %.12f   worst per-entry |difference| %.2e'
+             % (med(t[True]) / med(t[False]), res[False]['Cider'], res[True]['Cider'], res[False]['Bleu4'], res[True]['Bleu4'], worst)]
+    if not args.no_forward:
+        model, data, _ = build(args.batches, dev)
+        for _ in range(2):
+            forward_only(model, data)
+        fwd = [forward_only(model, data) for _ in range(args.repeats)]
+        n = args.batches * B
+        lines.append('  greedy forward alone, batch %d, %dx%d, %d batches: %.1f images/s (median of %d passes, spread %.1f%%): %d images take %.2f s'
+                     % (B, IMG[0], IMG[1], args.batches, n / med(fwd), args.repeats, 100 * (max(fwd) - min(fwd)) / med(fwd), N, N * med(fwd) / n))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--batches', type=int, default=8)
@@ -89,10 +167,16 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--trace-run', action='store_true', help='the short run meant to be traced: warm-up + two device-scored passes')
     ap.add_argument('--stats', default=None, help='rocprofv3 output directory to summarise')
+    ap.add_argument('--captions', action='store_true', help='the caption scoring pass (device scorer against host=True) instead of detection')
+    ap.add_argument('--no-forward', action='store_true', help='with --captions: skip the greedy forward beside the scorers')
     args = ap.parse_args()
     lines = []
     if args.stats:
         lines.append(stats(args.stats))
+    elif args.captions:
+        import torch
+        assert torch.cuda.is_available(), 'bench_eval.py measures on the GPU only'
+        lines += caption_pass(args, torch.device('cuda:0'))
     else:
         import torch
         assert torch.cuda.is_available(), 'bench_eval.py measures on the GPU only'
