@@ -5,6 +5,9 @@ piece, the vocabulary cross-entropy, is the HIP kernel (ops.softmax_ce).
 
 Reference: utils/box_ops.py, utils/matcher.py, utils/set_criterion.py, exp/gpv/models/losses.py.
 """
+import os
+
+import numpy as np
 import torch
 import torch.nn as nn
 from scipy.optimize import linear_sum_assignment
@@ -47,6 +50,121 @@ def generalized_box_iou(b1, b2):
     wh = (rb - lt).clamp(min=0)
     area = wh[:, :, 0] * wh[:, :, 1]
     return iou - (area - union) / area
+
+
+
+# ---------------------------------------------------------------- the matching rule, stated once on the host
+def lsap_host(cost):
+    """Linear sum assignment of one cost matrix, the rule csrc/set_match.hip runs on the device: scipy.optimize.linear_sum_assignment
+    restated (shortest augmenting paths with dual variables u, v; plain numpy, float64), ties included.
+      * more rows than columns: the transposed matrix is solved and the result is sorted by row;
+      * every path search starts with ``remaining`` = the columns in REVERSE order (nc-1 ... 0), all path costs +inf, minVal 0;
+      * one step of a search, for the current row i: first EVERY remaining column j gets r = minVal + c[i][j] - u[i] - v[j] (float64,
+        in that order) and keeps it when r < its path cost (then path[j] = i); then ONE column is picked among those at the minimum
+        path cost: the one at the LAST position of ``remaining`` that is unassigned, or, when none of them is unassigned, the one at
+        the FIRST position.  It leaves ``remaining`` by ``remaining[index] = remaining[--num_remaining]``.  An unassigned pick ends the
+        search (the sink); an assigned one makes its row the current row;
+      * then u[cur] += minVal, u[i] += minVal - pathcost[col4row[i]] for every other visited row, v[j] -= minVal - pathcost[j] for
+        every visited column, and the path is flipped from the sink back to the row the search started from.
+    "Update all, then pick" is what scipy's serial scan computes, so the update may run in parallel.
+    NaN or -inf in the cost raises ValueError (scipy does); a search that finds only +inf raises too.  -> (row_idx, col_idx) int64"""
+    c = np.asarray(cost, dtype=np.float64)
+    if c.ndim != 2:
+        raise ValueError(f'lsap_host: expected a matrix, got {c.ndim} dimensions')
+    if np.isnan(c).any() or np.isneginf(c).any():
+        raise ValueError('lsap_host: the cost matrix contains invalid numeric entries')
+    transpose = c.shape[1] < c.shape[0]
+    if transpose:
+        c = c.T
+    nr, nc = c.shape
+    if nr == 0 or nc == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    u, v = np.zeros(nr), np.zeros(nc)
+    path = np.full(nc, -1, np.int64)
+    col4row, row4col = np.full(nr, -1, np.int64), np.full(nc, -1, np.int64)
+    for cur in range(nr):
+        remaining = np.arange(nc - 1, -1, -1)
+        num_remaining = nc
+        spc = np.full(nc, np.inf)
+        SR, SC = np.zeros(nr, bool), np.zeros(nc, bool)
+        min_val, i, sink = 0.0, cur, -1
+        while sink == -1:
+            SR[i] = True
+            js = remaining[:num_remaining]
+            r = ((min_val + c[i, js]) - u[i]) - v[js]
+            better = r < spc[js]
+            path[js[better]] = i
+            spc[js[better]] = r[better]
+            vals = spc[js]
+            min_val = vals.min()
+            if min_val == np.inf:
+                raise ValueError('lsap_host: the cost matrix is infeasible')
+            at_min = np.flatnonzero(vals == min_val)
+            free = at_min[row4col[js[at_min]] == -1]
+            index = free[-1] if len(free) else at_min[0]
+            j = js[index]
+            if row4col[j] == -1:
+                sink = j
+            else:
+                i = row4col[j]
+            SC[j] = True
+            num_remaining -= 1
+            remaining[index] = remaining[num_remaining]
+        u[cur] += min_val
+        for r_ in np.flatnonzero(SR):
+            if r_ != cur:
+                u[r_] += min_val - spc[col4row[r_]]
+        v[SC] -= min_val - spc[SC]
+        j = sink
+        while True:
+            i = path[j]
+            row4col[j] = i
+            col4row[i], j = j, col4row[i]
+            if i == cur:
+                break
+    if transpose:
+        order = np.argsort(col4row, kind='stable')
+        return col4row[order].astype(np.int64), order.astype(np.int64)
+    return np.arange(nr, dtype=np.int64), col4row.astype(np.int64)
+
+
+def match_cost_host(logits, boxes, tgt_boxes, labels, w_class, w_bbox, w_giou):
+    """The matching cost of one image, the rule csrc/set_match.hip evaluates on the device: fp32, a FIXED order of operations, every
+    product and sum rounded on its own (numpy float32 arrays do exactly that).  logits [Q,C+1], boxes [Q,4] and tgt_boxes [G,4]
+    cxcywh, labels [G].
+      p    = softmax(logits)[label]: e_k = exp(x_k - max_k x_k), summed in class order, p = e_label / sum
+      l1   = ((|dcx| + |dcy|) + |dw|) + |dh|
+      giou = from the corners (cx -+ 0.5 w, cy -+ 0.5 h), as generalized_box_iou orders it: union = (a1 + a2) - inter,
+             iou = inter / union, area = enclosing box, giou = iou - (area - union) / area
+      cost = (w_bbox * l1 + w_class * (-p)) + w_giou * (-giou)
+    It is the same formula as HungarianMatcher.forward but not bit-equal to torch's cdist / softmax kernels, and is not meant to be:
+    the device matcher has to agree with THIS statement.  -> [Q,G] float32"""
+    f = np.float32
+    x = np.asarray(logits, f)
+    pb, tb = np.asarray(boxes, f), np.asarray(tgt_boxes, f)
+    labels = np.asarray(labels, np.int64)
+    e = np.exp(x - x.max(-1, keepdims=True))
+    total = np.zeros(x.shape[0], f)
+    for k in range(x.shape[1]):
+        total = total + e[:, k]
+    p = e[:, labels] / total[:, None]
+    d = np.abs(pb[:, None, :] - tb[None, :, :])
+    l1 = ((d[..., 0] + d[..., 1]) + d[..., 2]) + d[..., 3]
+    half = f(0.5)
+
+    def corners(b):
+        return b[:, 0] - half * b[:, 2], b[:, 1] - half * b[:, 3], b[:, 0] + half * b[:, 2], b[:, 1] + half * b[:, 3]
+
+    ax0, ay0, ax1, ay1 = (t[:, None] for t in corners(pb))
+    bx0, by0, bx1, by1 = (t[None, :] for t in corners(tb))
+    a1, a2 = (ax1 - ax0) * (ay1 - ay0), (bx1 - bx0) * (by1 - by0)
+    zero = f(0)
+    inter = np.maximum(np.minimum(ax1, bx1) - np.maximum(ax0, bx0), zero) * np.maximum(np.minimum(ay1, by1) - np.maximum(ay0, by0), zero)
+    union = (a1 + a2) - inter
+    iou = inter / union
+    area = np.maximum(np.maximum(ax1, bx1) - np.minimum(ax0, bx0), zero) * np.maximum(np.maximum(ay1, by1) - np.minimum(ay0, by0), zero)
+    giou = iou - (area - union) / area
+    return ((f(w_bbox) * l1 + f(w_class) * (-p)) + f(w_giou) * (-giou)).astype(f)
 
 
 # ---------------------------------------------------------------- matcher.py:32-77
@@ -171,18 +289,85 @@ class ClsLoss(AnswerClassification):
     task, key = 'CocoClassification', 'loss_cls'
 
 
+class _DeviceIndices:
+    """the main layer's matching of a device-matcher call, in SetCriterion.last_indices' format -- a list of (int64, int64) CPU
+    pairs, one per localisation sample -- materialised when first read: that read is the device-to-host copy (the sync), and the place
+    where the kernels' status words are checked"""
+
+    def __init__(self, pred, tgt, n_pairs, status, sel):
+        self._dev, self._sel, self._list = (pred, tgt, n_pairs, status), sel, None
+
+    def _get(self):
+        if self._list is None:
+            from . import hip_match
+            pred, tgt, n, status = (t.cpu() for t in self._dev)
+            hip_match.check_status(status.tolist())
+            self._list = [(pred[b, :int(n[b])].to(torch.int64), tgt[b, :int(n[b])].to(torch.int64)) for b in self._sel]
+            self._dev = None
+        return self._list
+
+    def __iter__(self):
+        return iter(self._get())
+
+    def __len__(self):
+        return len(self._sel)
+
+    def __getitem__(self, i):
+        return self._get()[i]
+
+
 class Localization(nn.Module):
+    """cfg.matcher (absent: 'host'; the environment variable GPV_MATCHER overrides it) chooses where box batches are matched:
+    'host'   -- HungarianMatcher (cost on the device, .cpu(), scipy per image) + SetCriterion, the reference's path;
+    'device' -- csrc/set_match.hip through ops.device_set_criterion: main and aux layers in one call, no host sync, fixed shapes."""
+
     def __init__(self, cfg):
         super().__init__()
         self.matcher = HungarianMatcher(cost_class=cfg.cost_wts.ce, cost_bbox=cfg.cost_wts.bbox,
                                         cost_giou=cfg.cost_wts.giou)
         self.set_criterion = SetCriterion(num_classes=cfg.num_classes, matcher=self.matcher, weight_dict=None,
                                           eos_coef=cfg.eos_coef, losses=['labels', 'boxes'])
+        self.matcher_mode = os.environ.get('GPV_MATCHER') or cfg.get('matcher', 'host')     # device | host: where box batches are matched; overrides the loss config's `matcher` key (DESIGN 6c)
+        if self.matcher_mode not in ('host', 'device'):
+            raise ValueError(f"Localization: matcher must be 'host' or 'device', got {self.matcher_mode!r}")
+        self.cost_wts = (float(cfg.cost_wts.ce), float(cfg.cost_wts.bbox), float(cfg.cost_wts.giou))
+
+    def forward_device(self, outputs, targets, sel):
+        """one ops.device_set_criterion call for the main and the aux layers.  Targets are padded to [B, Gmax]; g_count comes from the
+        host-known lengths (-1: the sample has no 'boxes' key and takes no part), which is shape information and needs no sync."""
+        from . import hip_match
+        layers = [outputs] + list(outputs.get('aux_outputs', ()))
+        logits = torch.stack([o['pred_relevance_logits'] for o in layers]).float()
+        boxes = torch.stack([o['pred_boxes'] for o in layers]).float()
+        if not logits.is_cuda:
+            raise RuntimeError("gpv1_amd: matcher='device' needs the outputs on the GPU (no CPU fallback exists for the device matcher)")
+        dev = logits.device
+        B, Q = logits.shape[1], logits.shape[2]
+        counts = [len(targets[i]['boxes']) if 'boxes' in targets[i] else -1 for i in range(B)]
+        gmax = max(max(counts), 1)
+        if not hip_match.supported(Q, gmax) or logits.shape[3] > hip_match.MAX_CLASSES:
+            return None                                           # larger than the kernels take: the host path runs for this call
+        rows = [b * gmax + k for b in sel for k in range(counts[b])]
+        meta = torch.tensor(counts + rows, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        g_count, rows = meta[:B].to(torch.int32), meta[B:]
+        tgt_boxes = torch.zeros(B * gmax, 4, dtype=torch.float32, device=dev)
+        tgt_labels = torch.zeros(B * gmax, dtype=torch.int32, device=dev)
+        if rows.numel():
+            tgt_boxes.index_copy_(0, rows, torch.cat([targets[b]['boxes'] for b in sel]).float().to(dev))
+            tgt_labels.index_copy_(0, rows, torch.cat([targets[b]['labels'] for b in sel]).to(device=dev, dtype=torch.int32))
+        ce, bbox, giou, pred, tgt, n_pairs, status = ops.device_set_criterion(
+            logits, boxes, tgt_boxes.view(B, gmax, 4), tgt_labels.view(B, gmax), g_count, self.cost_wts, self.set_criterion.eos_coef)
+        self.set_criterion.last_indices = _DeviceIndices(pred[:B], tgt[:B], n_pairs[:B], status, sel)
+        return {'loss_ce': ce.sum(), 'loss_bbox': bbox.sum(), 'loss_giou': giou.sum()}
 
     def forward(self, outputs, targets):
         sel = [i for i, t in enumerate(targets) if 'boxes' in t]
         if not sel:
             return {'loss_ce': None, 'loss_bbox': None, 'loss_giou': None}
+        if self.matcher_mode == 'device':
+            ret = self.forward_device(outputs, targets, sel)
+            if ret is not None:
+                return ret
         fo = {'pred_relevance_logits': outputs['pred_relevance_logits'][sel], 'pred_boxes': outputs['pred_boxes'][sel]}
         if 'aux_outputs' in outputs:
             fo['aux_outputs'] = [{'pred_relevance_logits': a['pred_relevance_logits'][sel], 'pred_boxes': a['pred_boxes'][sel]}

@@ -1411,6 +1411,49 @@ def softmax_ce(logits, target):
 
 
 # --------------------------------------------------------------------------------------------
+# Hungarian matching + DETR set criterion on the device (csrc/set_match.hip through hip_match)
+# --------------------------------------------------------------------------------------------
+class DeviceSetCriterionFn(Function):
+    """match (gpv_match_boxes), then loss (gpv_match_set_loss): two launches and a handful of fixed-shape torch ops, over tensors
+    only -- no host sync, no data-dependent shape, so the call can be captured.  The kernels leave per-(l, b) sums and unnormalised
+    gradients; the normalisation (loss_ce = num / den per layer, the box sums over num_boxes, which the loss kernel computes on the
+    device) happens here, and backward only scales the saved gradients."""
+
+    @staticmethod
+    def forward(ctx, logits, boxes, tgt_boxes, tgt_labels, g_count, w_class, w_bbox, w_giou, eos_coef):
+        from . import hip_match
+        lg, bx = logits.contiguous(), boxes.contiguous()
+        pred, tgt, n_pairs, status, _ = hip_match.match_boxes(lg, bx, tgt_boxes, tgt_labels, g_count, w_class, w_bbox, w_giou)
+        partial, dlogits, dl1, dgi, nb = hip_match.set_loss(lg, bx, tgt_boxes, tgt_labels, g_count, pred, tgt, n_pairs, status, eos_coef)
+        sums = partial.sum(1)                                                   # [L, 4] float64, a fixed-order reduction over B
+        ce, bbox, giou = sums[:, 0] / sums[:, 1], sums[:, 2] / nb, sums[:, 3] / nb
+        ctx.save_for_backward(dlogits, dl1, dgi, sums[:, 1].contiguous(), nb)
+        ctx.mark_non_differentiable(pred, tgt, n_pairs, status)
+        return ce.float(), bbox.float(), giou.float(), pred, tgt, n_pairs, status
+
+    @staticmethod
+    def backward(ctx, g_ce, g_bbox, g_giou, *_):
+        dlogits, dl1, dgi, den, nb = ctx.saved_tensors
+        L = dlogits.shape[0]
+        dl = dbx = None
+        if ctx.needs_input_grad[0]:
+            dl = dlogits * (g_ce.double() / den).float().view(L, 1, 1, 1)
+        if ctx.needs_input_grad[1]:
+            dbx = dl1 * (g_bbox.double() / nb).float().view(L, 1, 1, 1) + dgi * (g_giou.double() / nb).float().view(L, 1, 1, 1)
+        return dl, dbx, None, None, None, None, None, None, None
+
+
+def device_set_criterion(logits, boxes, tgt_boxes, tgt_labels, g_count, cost_wts, eos_coef):
+    """logits [L,B,Q,C+1], boxes [L,B,Q,4] fp32 (layer 0 = the main outputs), tgt_boxes [B,Gmax,4] fp32, tgt_labels [B,Gmax],
+    g_count [B] int32 (-1: the sample takes no part in localisation, 0: a detection sample without boxes); cost_wts = (class, bbox,
+    giou).  -> loss_ce [L], loss_bbox [L], loss_giou [L] (differentiable in logits and boxes) and the matching it used:
+    pred_idx [L*B,K], tgt_idx [L*B,K], n_pairs [L*B], status [L*B] int32 (hip_match.check_status after a copy to the host)."""
+    w_class, w_bbox, w_giou = cost_wts
+    return DeviceSetCriterionFn.apply(logits, boxes, tgt_boxes, tgt_labels, g_count, float(w_class), float(w_bbox), float(w_giou),
+                                      float(eos_coef))
+
+
+# --------------------------------------------------------------------------------------------
 # RoIAlign(7x7, aligned) + mean over bins, separable form (detr_roi_head.py:44-56)
 # --------------------------------------------------------------------------------------------
 class RoiPoolFn(Function):
