@@ -568,6 +568,10 @@ class FlatTrainer:
     max_norm / (|average| + 1e-6) -- the epsilon weighs 1 / world as much (1e-6 against norms of 1e-1 .. 1e2: below fp32 resolution
     of the factor for world <= 8)."""
 
+    # health.FlightRecorder or None: when set, train_step calls recorder.record() once the step's gradients are final (after the
+    # gradient exchange) and before step(); with None the trainer issues exactly the launches it issues without the feature
+    recorder = None
+
     @property
     def grad_scale(self):
         """what turns G / p.grad (sums over ranks after the exchange) into the reference's averaged gradients"""
@@ -1084,6 +1088,8 @@ class FlatTrainer:
             loss.backward()
         ops_check_chains()
         self.allreduce_grads()
+        if self.recorder is not None:
+            self.recorder.record()
         self.step()
         return None if loss is None else loss.detach()     # (a stashed loss would keep the step's autograd graph alive)
 
@@ -1245,6 +1251,8 @@ class FlatTrainer:
                 if loss is not None:
                     loss.backward()
         self.allreduce_grads()
+        if self.recorder is not None:
+            self.recorder.record()
         self.step()
         if hp is not None:
             hp['optimizer'] = hp.get('optimizer', 0.0) + time.perf_counter() - t0

@@ -272,6 +272,13 @@ def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
     trainer = FlatTrainer(model, lr=tr_cfg.lr, lr_backbone=tr_cfg.lr_backbone, weight_decay=tr_cfg.weight_decay,
                           clip_max_norm=tr_cfg.clip_max_norm,
                           warmup_steps=int(tr_cfg.lr_warmup_fraction * t_total) if tr_cfg.lr_warmup else 0, t_total=t_total, **sched)
+    # training.health (optional, not in the default tree): {every, ring, watch, on_nonfinite} -> the flight recorder (health.py)
+    health_cfg, recorder = tr_cfg.get('health', None), None
+    if health_cfg:
+        from .health import FlightRecorder
+        recorder = trainer.recorder = FlightRecorder(trainer, watch=tuple(health_cfg.get('watch', None) or ('G',)),
+                                                     ring=int(health_cfg.get('ring', 64)), every=int(health_cfg.get('every', 1)),
+                                                     on_nonfinite=health_cfg.get('on_nonfinite', 'raise'))
     step, last_epoch, best_metric, said = 0, -1, 0.0, set()
     if have_ckpt:
         ckpt, taken = load_checkpoint(tr_cfg.ckpt, model, trainer, map_location=device)
@@ -313,8 +320,18 @@ def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
             loss = trainer.train_step(imgs, queries, targets)
             step += 1
             if rank == 0 and step % tr_cfg.log_step == 0:
-                log(f'epoch {epoch} step {step} loss {float(loss.detach()) if loss is not None else float("nan"):.4f} '
-                    f'lr {trainer.current_lrs()["others"]:.3e} {time.time() - t0:.1f}s')
+                line = (f'epoch {epoch} step {step} loss {float(loss.detach()) if loss is not None else float("nan"):.4f} '
+                        f'lr {trainer.current_lrs()["others"]:.3e} {time.time() - t0:.1f}s')
+                reading = recorder.read() if recorder is not None else None       # (behind the loss read above, which already waited)
+                if reading is not None and reading.commits:
+                    norms = reading.grad_norms()
+                    if norms is not None:
+                        line += ' gnorm ' + ' '.join(f'{g} {v:.4e}' for g, v in norms.items())
+                log(line)
+                if reading is not None and reading.trip is not None:
+                    if not recorder._warned:
+                        recorder.write_report(reading, os.path.join(cfg.ckpt_dir, 'nonfinite_report.json'))
+                    recorder.check(reading)                                       # raises, or warns once (on_nonfinite)
             if rank == 0 and step % tr_cfg.ckpt_step == 0:
                 # like the reference's mid-epoch save (train_distr.py:372-389: 'epoch': epoch-1 next to the CURRENT step): a
                 # resume re-runs this epoch from its start while the schedule continues from `step` -- the reference's behaviour,
