@@ -18,6 +18,11 @@
 // oracle restates the same formulas and the step is "parity unpinned" against the real libraries):
 //   grey L = (19595 R + 38470 G + 7471 B + 32768) >> 16;  brightness b: round(clip(b x));  contrast c: round(clip(m + c (x - m))),
 //   m = floor(mean(L) + 0.5);  saturation s: round(clip(L + s (x - L)));  hue h: RGB -> HSV (float), H += h mod 1, -> RGB, round.
+// A negative entry of order[] is "no step" (ColorJitter(0.2, 0.2, 0.2, 0) of the generic datasets has three: the hue round trip is
+// not the identity on uint8, so it cannot stand in for a missing step).
+// A source may be a WINDOW of a larger image (CocoClassification.read_image cuts the box out before the resize,
+// datasets/coco_datasets.py:152-175): src points at the window's first pixel (any byte address), H x W is the window, pitch the
+// row length of the image around it.  Mirroring happens at the window's borders, so no tap leaves the window.
 #include "common.h"
 #include "../../include/gpv_hip.h"
 
@@ -37,6 +42,7 @@ __device__ __forceinline__ float grey(float r, float g, float b) {
 
 // one colour step on uint8-valued floats; mgrey = the image's mean grey for the contrast step
 __device__ __forceinline__ void color_step(int op, const gpv_image_desc& d, float mgrey, float& r, float& g, float& b) {
+  if (op < 0) return;                              // no step
   if (op == 0) {
     r = rintf(clip255(r * d.brightness)); g = rintf(clip255(g * d.brightness)); b = rintf(clip255(b * d.brightness));
   } else if (op == 1) {
@@ -81,6 +87,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const gpv_image_desc* __res
   const int b = blockIdx.y;
   const gpv_image_desc d = descs[b];
   const int n = OH * OW;
+  const int64_t pitch = d.pitch ? d.pitch : d.W;   // source row length in pixels (a window of a larger image)
   const float sy = (float)d.H / OH, sx = (float)d.W / OW;
   const float sgy = fmaxf(0.f, (sy - 1.f) * 0.5f), sgx = fmaxf(0.f, (sx - 1.f) * 0.5f);
   const int ry = sgy > 0.f ? (int)(4.f * sgy + 0.5f) : 0, rx = sgx > 0.f ? (int)(4.f * sgx + 0.5f) : 0;
@@ -115,7 +122,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const gpv_image_desc* __res
           float rowv[3] = {0.f, 0.f, 0.f};
           for (int kx = -rx; kx <= rx; ++kx) {
             const int xx = mirror(x0 + tx + kx, d.W);
-            const uint8_t* px = d.src + ((int64_t)yy * d.W + xx) * 3;
+            const uint8_t* px = d.src + (yy * pitch + xx) * 3;    // yy < H, xx < W: inside the window
             const float wk = wx[kx + rx];
             rowv[0] += wk * px[0]; rowv[1] += wk * px[1]; rowv[2] += wk * px[2];
           }
@@ -130,7 +137,10 @@ __global__ __launch_bounds__(256) void resize_kernel(const gpv_image_desc* __res
     uint8_t* o = tmp + ((int64_t)b * n + i) * 3;
     o[0] = (uint8_t)r; o[1] = (uint8_t)g; o[2] = (uint8_t)bl;
     if (d.jitter) {                                // grey of the image as it enters the contrast step
-      for (int k = 0; k < 4 && d.order[k] != 1; ++k) color_step(d.order[k], d, 0.f, r, g, bl);
+      for (int k = 0; k < 4 && d.order[k] != 1; ++k) {
+        if (d.order[k] < 0) continue;
+        color_step(d.order[k], d, 0.f, r, g, bl);
+      }
       lsum += (unsigned)grey(r, g, bl);
     }
   }
@@ -161,7 +171,10 @@ __global__ __launch_bounds__(256) void color_kernel(const gpv_image_desc* __rest
       const uint8_t* px = tmp + ((int64_t)b * OH * OW + (int64_t)y * OW + xs) * 3;
       float r = px[0], g = px[1], bl = px[2];
       if (d.jitter) {
-        for (int k = 0; k < 4; ++k) color_step(d.order[k], d, mgrey, r, g, bl);
+        for (int k = 0; k < 4; ++k) {
+          if (d.order[k] < 0) continue;
+          color_step(d.order[k], d, mgrey, r, g, bl);
+        }
       }
       if (d.gray) { const float l = grey(r, g, bl); r = g = bl = l; }
       v[0] = (r / 255.f - mean[0]) * istd[0];

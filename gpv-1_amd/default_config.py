@@ -85,6 +85,8 @@ _TREE = {'exp_name': 'default',
               'num_epochs': 40,
               'batch_size': 120,
               'num_workers': 30,
+              'data_source': 'synthetic',          # 'files': CocoMultitaskDataset(learning_datasets, task_configs) behind a DeviceLoader
+              'prefetch': 1,                       # batches the loader's worker thread prepares ahead (data_source: files)
               'vis_step': 2000,
               'log_step': 10,
               'ckpt_step': 2000,
@@ -110,6 +112,26 @@ _TREE = {'exp_name': 'default',
           'num_output_boxes': 5,
           'beam_size': 5}}
 
+
+# configs/task/coco_learning_tasks.yaml (`# @package task_configs`): where the preprocessed sample files and the images lie.
+# Settings only; gpv1_amd.datasets reads them.
+def _task(samples, subsets=('train', 'val', 'test'), **more):
+    return dict({'image_dir': '${task_configs.image_dir}', 'image_size': '${task_configs.image_size}', 'read_image': '${task_configs.read_image}'},
+                **more, samples={s: samples.replace('SUBSET', s) for s in subsets}, max_samples={s: None for s in subsets})
+
+
+_LPD = '${data_dir}/learning_phase_data'
+_TREE['task_configs'] = {
+    'image_dir': _LPD + '/coco/images',
+    'image_size': {'H': 480, 'W': 640},
+    'read_image': True,
+    'data_split': 'gpv_split',
+    'coco_captioning': _task(_LPD + '/coco_captions/${task_configs.data_split}/SUBSET.json'),
+    'coco_detection': _task(_LPD + '/coco_detection/${task_configs.data_split}/SUBSET.json'),
+    'coco_classification': _task(_LPD + '/coco_classification/${task_configs.data_split}/SUBSET.json'),
+    'coco_vqa': _task(_LPD + '/vqa/${task_configs.data_split}/SUBSET.json', subsets=('train', 'val', 'test', 'testdev')),
+    'refcocop': _task(_LPD + '/refcocop/SUBSET.json', train_percent=100)}
+_TREE['task_configs']['refcocop']['samples']['train'] = _LPD + '/refcocop/train_${task_configs.refcocop.train_percent}.json'
 
 # configs/learning_datasets/*.yaml: the task mixes `learning_datasets=<name>` selects (scripts/train.sh:14-34); `vqa` is the
 # default of configs/exp/gpv.yaml:25

@@ -88,7 +88,7 @@ class JpegDesc(C.Structure):
 class ImageDesc(C.Structure):
     _fields_ = [('src', C.c_void_p), ('H', C.c_int), ('W', C.c_int), ('flip', C.c_int), ('gray', C.c_int), ('jitter', C.c_int),
                 ('order', C.c_int * 4), ('brightness', C.c_float), ('contrast', C.c_float), ('saturation', C.c_float),
-                ('hue', C.c_float), ('reserved', C.c_int)]
+                ('hue', C.c_float), ('pitch', C.c_int)]
 
 
 def lib():

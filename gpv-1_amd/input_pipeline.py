@@ -2,8 +2,10 @@
 
 Reference: datasets/coco_generic_dataset.py:49-62 (``resize(img, (imh, imw), anti_aliasing=True)``), datasets/coco_datasets.py
 (:26-38 detection, :137-150 classification: ``ToPILImage -> RandomApply([ColorJitter(0.4, 0.4, 0.4, 0.1)], p=0.8) ->
-[RandomHorizontalFlip] -> RandomGrayscale(p=0.2) -> ToTensor -> Normalize``; the other tasks: ToTensor -> Normalize only),
-30 CPU worker processes (configs/exp/gpv.yaml:126).
+[RandomHorizontalFlip] -> RandomGrayscale(p=0.2) -> ToTensor -> Normalize``; coco_generic_dataset.py:25-33, captioning and VQA on
+the train subset: ``RandomApply([ColorJitter(0.2, 0.2, 0.2, 0.0)], p=0.8)``; every other subset: ToTensor -> Normalize only),
+30 CPU worker processes (configs/exp/gpv.yaml:126).  ``DeviceImagePipeline(images, tasks)`` draws from the ``AUGMENT`` table below,
+which knows the two box tasks only; the per-class, per-subset rules live in gpv1_amd.datasets, which passes a ``spec``.
 
 Here the host only decodes (out of scope: JPEG) and draws the random parameters in torchvision's order; everything per pixel runs
 in two HIP launches (csrc/image_pipeline.hip) and lands in the layout the fused stem kernel reads, so neither an fp32 NCHW batch
@@ -30,22 +32,29 @@ JITTER = (0.4, 0.4, 0.4, 0.1)            # brightness, contrast, saturation, hue
 AUGMENT = {'CocoDetection': ('jitter', 'gray'), 'CocoClassification': ('jitter', 'flip', 'gray')}
 
 
-def draw_params(task, rng, train=True):
+def draw_params(task, rng, train=True, spec=None):
     """the random decisions of the reference's transform for one sample, in torchvision's order of draws:
-    RandomApply(p=0.8) -> ColorJitter.get_params (factors, then a random order of the four steps) -> RandomHorizontalFlip(0.5)
-    -> RandomGrayscale(0.2).  -> dict(jitter, order, brightness, contrast, saturation, hue, flip, gray)"""
+    RandomApply(p=0.8) -> ColorJitter.get_params (factors, then a random order of the steps) -> RandomHorizontalFlip(0.5)
+    -> RandomGrayscale(0.2).  -> dict(jitter, order, brightness, contrast, saturation, hue, flip, gray)
+    spec: None (the AUGMENT table's entry for `task`) or (jitter 4-tuple | None, flip, gray).  A jitter component of 0 draws nothing
+    and contributes no step (torchvision 0.7's _check_input returns None for it), so `order` then has fewer than four entries."""
     p = {'jitter': 0, 'order': (0, 1, 2, 3), 'brightness': 1.0, 'contrast': 1.0, 'saturation': 1.0, 'hue': 0.0, 'flip': 0, 'gray': 0}
-    aug = AUGMENT.get(task, ()) if train else ()
-    if 'jitter' in aug and rng.random() < 0.8:
-        b, c, s, h = JITTER
-        p.update(jitter=1, brightness=rng.uniform(max(0.0, 1 - b), 1 + b), contrast=rng.uniform(max(0.0, 1 - c), 1 + c),
-                 saturation=rng.uniform(max(0.0, 1 - s), 1 + s), hue=rng.uniform(-h, h))
-        order = [0, 1, 2, 3]
+    if spec is None:
+        aug = AUGMENT.get(task, ())
+        spec = (JITTER if 'jitter' in aug else None, 'flip' in aug, 'gray' in aug)
+    jitter, flip, gray = spec if train else (None, False, False)
+    if jitter is not None and rng.random() < 0.8:
+        p['jitter'] = 1
+        order = []
+        for step, (name, j) in enumerate(zip(('brightness', 'contrast', 'saturation', 'hue'), jitter)):
+            if j:
+                p[name] = rng.uniform(-j, j) if name == 'hue' else rng.uniform(max(0.0, 1 - j), 1 + j)
+                order.append(step)
         rng.shuffle(order)
         p['order'] = tuple(order)
-    if 'flip' in aug and rng.random() < 0.5:
+    if flip and rng.random() < 0.5:
         p['flip'] = 1
-    if 'gray' in aug and rng.random() < 0.2:
+    if gray and rng.random() < 0.2:
         p['gray'] = 1
     return p
 
@@ -61,30 +70,46 @@ class DeviceImagePipeline:
         self.size, self.train, self.rng, self.device = tuple(size), train, random.Random(seed), torch.device(device)
         self._scratch = {}
 
-    def __call__(self, images, tasks=None, params=None):
+    def __call__(self, images, tasks=None, params=None, crops=None):
         """images: list of HxWx3 uint8 arrays / tensors (host or device); tasks: list[str] (which augmentation applies);
-        params: optional list of draw_params() dicts (tests) -- drawn here otherwise"""
+        params: optional list of draw_params() dicts (the datasets, tests) -- drawn here otherwise; `order` may have fewer than four
+        entries; crops: optional list of None | (y1, y2, x1, x2) in source pixels: the sample is that window of its image (the
+        classification crop) -- the kernel reads it in place through the descriptor's pitch: no copy, no extra launch"""
         B = len(images)
         H, W = self.size
         Hp, Wp = stem_geometry(H, W)
         dev = self.device
         if params is None:
             params = [draw_params(tasks[i] if tasks is not None else None, self.rng, self.train) for i in range(B)]
-        srcs = []
-        for im in images:
+        if crops is None:
+            crops = [None] * B
+        if len(params) != B or len(crops) != B:
+            raise ValueError('DeviceImagePipeline: one params entry and one crops entry per image')
+        srcs, wins = [], []
+        for i, (im, crop) in enumerate(zip(images, crops)):
             t = torch.as_tensor(im)
             if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
                 raise ValueError('DeviceImagePipeline: images must be HxWx3 uint8 (decode / grey->RGB on the host, as the reference does)')
-            if max(t.shape[0] / H, t.shape[1] / W) > 9:
+            y1, y2, x1, x2 = (0, t.shape[0], 0, t.shape[1]) if crop is None else (int(v) for v in crop)
+            if not (0 <= y1 < y2 <= t.shape[0] and 0 <= x1 < x2 <= t.shape[1]):
+                raise ValueError(f'DeviceImagePipeline: window rows {y1}:{y2}, columns {x1}:{x2} of image {i} is empty or outside '
+                                 f'its {t.shape[0]} x {t.shape[1]} image')
+            if max((y2 - y1) / H, (x2 - x1) / W) > 9:
                 raise ValueError('DeviceImagePipeline: more than 9x down-scaling is not supported')
             if not t.is_cuda:
                 t = t.contiguous().pin_memory().to(dev, non_blocking=True)
             srcs.append(t.contiguous())
+            wins.append((y1, y2, x1, x2))
         descs = (hip.ImageDesc * B)()
-        for d, t, p in zip(descs, srcs, params):
-            d.src, d.H, d.W = t.data_ptr(), t.shape[0], t.shape[1]
+        for d, t, p, (y1, y2, x1, x2) in zip(descs, srcs, params, wins):
+            d.src, d.H, d.W, d.pitch = t.data_ptr() + (y1 * t.shape[1] + x1) * 3, y2 - y1, x2 - x1, t.shape[1]
+            if not (d.pitch == 0 or d.pitch >= d.W):         # (gpv_image_pipeline sees the descriptors in device memory only)
+                raise ValueError('DeviceImagePipeline: pitch must be 0 or at least the window width')
             d.flip, d.gray, d.jitter = int(p['flip']), int(p['gray']), int(p['jitter'])
-            d.order[:] = list(p['order'])
+            order = [int(o) for o in p['order']]
+            if len(order) > 4 or any(o > 3 for o in order):
+                raise ValueError(f"DeviceImagePipeline: order {p['order']!r} is not a list of at most four steps 0..3")
+            d.order[:] = order + [-1] * (4 - len(order))      # a negative entry is "no step"
             d.brightness, d.contrast, d.saturation, d.hue = p['brightness'], p['contrast'], p['saturation'], p['hue']
         raw = upload_bytes(bytes(descs), dev)
         key = (B, H, W)

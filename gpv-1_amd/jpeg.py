@@ -22,6 +22,15 @@ from . import hip
 from .misc import upload_bytes
 
 
+class ParsedBatch:
+    """what DeviceJpegDecoder.parse leaves for issue: per file the header (hip.JpegInfo) and the start of its coefficients in
+    `coefs` (CPU int16 tensor); lent: `coefs` is the caller's buffer (pinned by its owner), not pageable memory of our own"""
+
+    def __init__(self, infos, starts, coefs, lent):
+        self.infos, self.starts, self.coefs, self.lent = infos, starts, coefs, lent
+        self.slot = None                                 # the decoder's own ring slot, when __call__ lent it
+
+
 class DeviceJpegDecoder:
     def __init__(self, device='cuda', threads=8, slots=3, max_pixels=64 << 20):
         """max_pixels: refuse files whose header declares more than this many pixels (default 64 MPix; COCO's largest is 0.4) BEFORE
@@ -35,21 +44,26 @@ class DeviceJpegDecoder:
         self._stage, self._events, self._turn = [None] * slots, [None] * slots, 0
         self._keep = None
 
-    def _staging(self, n):
-        k = self._turn
-        self._turn = (k + 1) % len(self._stage)
-        if self._events[k] is not None:
-            self._events[k].synchronize()
+    def _staging(self, n, slot=None):
+        """-> (slot, its whole pinned buffer of at least n elements); slot: one this batch already holds (it grows), else the next in turn"""
+        k = slot
+        if k is None:
+            k = self._turn
+            self._turn = (k + 1) % len(self._stage)
+            if self._events[k] is not None:
+                self._events[k].synchronize()
         if self._stage[k] is None or self._stage[k].numel() < n:
             self._stage[k] = torch.empty(max(n, 1 << 22), dtype=torch.int16).pin_memory()
-        return k, self._stage[k][:n]
+        return k, self._stage[k]
 
-    def __call__(self, files):
-        """files: list of bytes objects (whole .jpg files) -> list of [H, W, 3] uint8 tensors on the device (asynchronous: ordered on
-        the current stream)"""
+    def parse(self, files, into=None):
+        """the HOST half: header pass + Huffman decoding of every file on the pool.  Makes no HIP call of any kind (no pinned
+        allocation, no event, no copy), so a worker thread may run it while the main thread captures a graph.
+        into: a CPU int16 tensor to decode into (the caller's pinned slot); when it is None or too small the coefficients go to
+        pageable memory and issue() stages them.  Or a callable n -> such a tensor of n elements, called once the header pass
+        knows the size: how __call__ takes a slot of its pinned ring (that one does make HIP calls: not for a worker thread).
+        -> ParsedBatch"""
         B = len(files)
-        if B == 0:
-            return []
         run = (lambda f, it: list(self.pool.map(f, it))) if self.pool is not None else (lambda f, it: [f(x) for x in it])
         infos = run(hip.jpeg_parse, files)                                            # header pass: sizes
         starts, total = [], 0
@@ -58,13 +72,32 @@ class DeviceJpegDecoder:
                 raise ValueError(f'DeviceJpegDecoder: file {i} declares {inf.width} x {inf.height} pixels, more than max_pixels = {self.max_pixels}')
             starts.append(total)
             total += int(inf.coef_count)
-        slot, stage = self._staging(total)                                            # one pinned buffer, one upload
-        run(lambda i: hip.jpeg_parse(files[i], stage[starts[i]:starts[i] + int(infos[i].coef_count)]), range(B))
+        if callable(into):
+            into = into(total)
+        lent = into is not None and into.numel() >= total
+        coefs = into[:total] if lent else torch.empty(total, dtype=torch.int16)
+        run(lambda i: hip.jpeg_parse(files[i], coefs[starts[i]:starts[i] + int(infos[i].coef_count)]), range(B))
+        return ParsedBatch(infos, starts, coefs, lent)
+
+    def issue(self, parsed, event=None):
+        """the DEVICE half: upload of the coefficients + the decode launches -> list of [H, W, 3] uint8 tensors on the device
+        (asynchronous: ordered on the current stream).  Coefficients that parse() left in pageable memory are staged through
+        the pinned ring here.  event: recorded behind the upload (the owner of a lent buffer waits on it before reusing it)."""
+        infos, starts, B = parsed.infos, parsed.starts, len(parsed.infos)
+        if B == 0:
+            return []
         dev = self.device
+        if parsed.lent:
+            slot, stage = parsed.slot, parsed.coefs
+        else:
+            slot, stage = self._staging(parsed.coefs.numel(), parsed.slot)            # one pinned buffer, one upload
+            stage = stage[:parsed.coefs.numel()]
+            stage.copy_(parsed.coefs)
         coefs = stage.to(dev, non_blocking=True)
-        ev = torch.cuda.Event()
+        ev = event if event is not None else torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        self._events[slot] = ev
+        if slot is not None:
+            self._events[slot] = ev
         pl_sizes = [sum(inf.bh[c] * inf.bw[c] * 64 for c in range(inf.ncomp)) for inf in infos]
         planes = torch.empty(sum(pl_sizes), dtype=torch.uint8, device=dev)
         outs = [torch.empty(inf.height, inf.width, 3, dtype=torch.uint8, device=dev) for inf in infos]
@@ -89,3 +122,18 @@ class DeviceJpegDecoder:
         hip.jpeg_decode(raw, B, max(p // 64 for p in pl_sizes), max(inf.width * inf.height for inf in infos))
         self._keep = (coefs, planes, raw)                     # operands of the asynchronous launches
         return outs
+
+    def __call__(self, files):
+        """files: list of bytes objects (whole .jpg files) -> list of [H, W, 3] uint8 tensors on the device (asynchronous: ordered on
+        the current stream)"""
+        if len(files) == 0:
+            return []
+        slot = []
+
+        def ring(n):                                          # one pinned buffer of the ring, sized by the header pass
+            k, stage = self._staging(n)
+            slot.append(k)
+            return stage
+        parsed = self.parse(files, into=ring)
+        parsed.slot = slot[0]
+        return self.issue(parsed)

@@ -25,10 +25,13 @@ What is reproduced -- everything between the data loader and the checkpoint file
     it is 0 and the log says so (the reference's pycocoevalcap is un-vendored); the reference leaves ``refcocop`` out of the
     sum, so its mAP is logged only.  Evaluation leaves the training state alone: ``model.eval()`` / ``no_grad`` /
     ``model.train()``, no RNG draw, the captured training graphs are replayed afterwards, not recaptured.
-Out of scope: dataset ETL, TensorBoard, HTML.  Without ``eval_datasets`` this driver checkpoints every
+Out of scope: dataset ETL (downloading / preprocessing COCO; READING what it wrote is gpv1_amd.datasets), TensorBoard, HTML.  Without ``eval_datasets`` this driver checkpoints every
 ``training.ckpt_step`` steps and at every epoch end into ``model.pth``.
 The dataset is any sequence of ``(image[3,H,W] fp32 normalised, query str | (ids, mask), target dict)``;
-``SyntheticCocoDataset`` provides BASELINE's synthetic COCO-shaped samples.  An evaluation dataset is such a sequence with
+``SyntheticCocoDataset`` provides BASELINE's synthetic COCO-shaped samples (``training.data_source: synthetic``, the default).
+``training.data_source: files`` reads the reference's preprocessed sample files and the COCO image directory that ``task_configs``
+names (gpv1_amd.datasets: ``CocoMultitaskDataset`` behind a ``DeviceLoader`` that prepares one batch ahead and feeds the
+device-side JPEG decoder and image pipeline); ``eval_datasets`` then defaults to the same mix on ``train`` and ``val``.  An evaluation dataset is such a sequence with
 a ``samples`` list beside it (the reference's ``dataset.samples``: the dicts the evaluators read), optionally ``synonyms``
 (classification) and ``scorer`` (captioning).
 """
@@ -90,7 +93,11 @@ def shard_indices(n, epoch, rank, world, seed=0):
     return idx[rank:total:world]
 
 
-def batches(dataset, indices, batch_size, device):
+def batches(dataset, indices, batch_size, device, epoch=0):
+    loader = getattr(dataset, 'loader', None)
+    if loader is not None:                     # gpv1_amd.datasets.DeviceLoader: files -> device-side decode and transform, one batch ahead
+        yield from loader.batches(indices, epoch, batch_size)
+        return
     for s in range(0, len(indices) - batch_size + 1, batch_size):
         items = [dataset[i] for i in indices[s:s + batch_size]]
         imgs = [it[0].to(device) for it in items]
@@ -107,6 +114,10 @@ def batches(dataset, indices, batch_size, device):
 
 def eval_batches(dataset, batch_size, device):
     """the evaluation loader (train_distr.py:336-341: shuffle=False, the last batch may be short)"""
+    loader = getattr(dataset, 'loader', None)
+    if loader is not None:
+        yield from loader.eval_batches(batch_size)
+        return
     n = len(dataset)
     for s in range(0, n, batch_size):
         items = [dataset[i] for i in range(s, min(n, s + batch_size))]
@@ -223,6 +234,28 @@ def load_checkpoint(path, model, trainer=None, map_location='cpu'):
     return ckpt, taken
 
 
+def file_datasets(cfg, batch_size, device, train=True, evals=True):
+    """training.data_source: files -- the reference's datasets behind DeviceLoaders (gpv1_amd.datasets):
+    -> (CocoMultitaskDataset(cfg.learning_datasets, cfg.task_configs, 'train') | None, {'train' | 'val': {name: dataset}} | None: the same
+    mix per name as train_distr.py:163-166 / :328-341 build it).  A missing sample file or image directory raises, naming the path."""
+    from .datasets import DATASETS, CocoMultitaskDataset, DeviceLoader
+    tr_cfg = cfg.training
+    kw = dict(device=device, threads=max(1, min(16, int(tr_cfg.get('num_workers', 8)))), prefetch=int(tr_cfg.get('prefetch', 1)))
+    if 'task_configs' not in cfg:
+        raise KeyError('training.data_source: files needs a task_configs tree (gpv1_amd.default_config)')
+    train_ds, eval_ds = None, None
+    if train:
+        train_ds = CocoMultitaskDataset(cfg.learning_datasets, cfg.task_configs, 'train', seed=int(cfg.get('seed', 0) or 0))
+        DeviceLoader(train_ds, batch_size, **kw)
+    for subset in ('train', 'val') if evals else ():
+        eval_ds = eval_ds or {}
+        eval_ds[subset] = {}
+        for cls_name, info in cfg.learning_datasets.items():
+            ds = eval_ds[subset][info['name']] = DATASETS[cls_name](cfg.task_configs[info['task_config']], subset)
+            DeviceLoader(ds, int(cfg.get('batch_size', None) or tr_cfg.batch_size), **kw)
+    return train_ds, eval_ds
+
+
 def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
     """one rank of the reference's ``train_worker``; returns (model, trainer, step).
     eval_datasets: None, or {'train' | 'val': {'coco_vqa' | 'coco_cls' | 'coco_cap' | 'coco_det' | 'refcocop': dataset}} -- evaluation
@@ -250,6 +283,15 @@ def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
     if tr_cfg.freeze:
         freeze_detr_params(model)
     model.to(device)
+    source, own_loaders = tr_cfg.get('data_source', 'synthetic'), []
+    if source not in ('synthetic', 'files'):
+        raise ValueError(f"training.data_source must be 'synthetic' or 'files', got {source!r}")
+    if dataset is None and source == 'files':
+        dataset, auto_evals = file_datasets(cfg, per_rank, device, evals=eval_datasets is None)
+        own_loaders.append(dataset.loader)
+        if eval_datasets is None:
+            eval_datasets = auto_evals
+            own_loaders += [ds.loader for sub in auto_evals.values() for ds in sub.values()]
     if dataset is None:
         # the task mix: configs/learning_datasets/<name>.yaml selected by `learning_datasets=<name>` (scripts/train.sh:14-34),
         # CocoMultitaskDataset(cfg.learning_datasets, ...) in the reference (train_distr.py:163-166)
@@ -314,7 +356,7 @@ def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
         launch = False
         idx = shard_indices(len(dataset), epoch, rank, world)
         epoch_done = True                     # False: max_steps ended the epoch before its last batch
-        batch_iter = iter(batches(dataset, idx, per_rank, device))
+        batch_iter = iter(batches(dataset, idx, per_rank, device, epoch))
         for it, (imgs, queries, targets) in enumerate(batch_iter):
             trainer.set_epoch(epoch, it)
             loss = trainer.train_step(imgs, queries, targets)
@@ -340,11 +382,14 @@ def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
             if max_steps is not None and step >= max_steps:
                 epoch_done = next(batch_iter, None) is None      # stopped on the epoch's last batch: the epoch is complete
                 break
+        batch_iter.close()                    # (a loader's worker thread is joined here when max_steps left the epoch early)
         stopped = max_steps is not None and step >= max_steps
         if rank == 0:
             save_checkpoint(ckpt_path, model, trainer, epoch if epoch_done else epoch - 1, step, best_metric)
         if stopped:
             break
+    for loader in own_loaders:                # the loaders this call built: their worker and pool threads end with it
+        loader.close()
     if world > 1:
         dist.barrier()
         from .misc import note_sync_collective

@@ -208,14 +208,18 @@ int gpv_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, int OH,
  * -> Normalize): B decoded uint8 HWC images of any size -> the stem's zero-padded NHWC4 batch out[B,Hp,Wp,4] (what
  * gpv_image_to_nhwc4 produces from a normalised fp32 batch).  descs: DEVICE array of B descriptors (the host draws the random
  * parameters); scratch_u8: B*OH*OW*3 bytes; grey_sum: B 32-bit words of scratch (an exact integer sum lives there).  order[] = the four jitter steps in the sample's drawn order
- * (0 brightness, 1 contrast, 2 saturation, 3 hue); jitter = 0 skips them.  Source side length / output side length <= 9. */
+ * (0 brightness, 1 contrast, 2 saturation, 3 hue), a negative entry is "no step"; jitter = 0 skips them all.  Source side length /
+ * output side length <= 9.  A source may be a window of a larger image (the classification crop, coco_datasets.py:152-175): src =
+ * the window's first pixel (no alignment assumed), H x W = the window's extent, pitch = the row length in pixels of the image it
+ * lies in (0 means W; otherwise pitch >= W, which the caller that fills the descriptors checks: they live in device memory here).
+ * Borders are mirrored at the window's edges and no pixel outside the window is read. */
 typedef struct gpv_image_desc {
-  const unsigned char* src;   /* [H][W][3] uint8, device */
+  const unsigned char* src;   /* [H][pitch][3] uint8, device: H rows of W pixels are read */
   int H, W;
   int flip, gray, jitter;
   int order[4];
   float brightness, contrast, saturation, hue;
-  int reserved;
+  int pitch;                  /* source row length in pixels; 0 = W */
 } gpv_image_desc;
 int gpv_image_pipeline(const gpv_image_desc* descs, int B, void* scratch_u8, float* grey_sum, void* out, int OH, int OW, int pad,
                        int Hp, int Wp, int dtype_out, void* stream);
