@@ -1,0 +1,132 @@
+"""The beam search step, stated once on the host (numpy, fp32 arithmetic in a fixed order): the rule that csrc/beam_step.hip runs on the
+device and that include/gpv_beam.h repeats word for word.
+
+Step t (0 <= t < T-1), batch element b, parent k1 = 0..K-1, logits row r = k1*B + b:
+ 1. x_v = fp32(logit[r, v]) + vocab_mask[v]: one fp32 add; no add when the mask is absent.
+ 2. lse_r = m + logf(sum_v expf(x_v - m)), m = max_v x_v, fp32.  The summation order is the kernel's own; lse is an OUTPUT of the device
+    step ([K*B] fp32) and an INPUT here, so no transcendental is evaluated on both sides and everything below is bit-exact.
+ 3. The row's candidates are its K largest x_v, ties to the lower v; k2 is the rank.  lp = x_v - lse_r: one fp32 subtract.
+ 4. score(k1,k2) = seq_lp[b,k1] + lp: one fp32 add.  t == 0 and k1 > 0: score = -1e9 exactly.  Mode FREEZE with finished[b,k1] set: the
+    parent has exactly one candidate, k2 = 0, token pad_id, score = seq_lp[b,k1] unchanged; its other candidates do not exist.
+ 5. key = score * inv_pen[len']: one fp32 multiply, len' = length[b,k1] + (finished[b,k1] ? 0 : 1) (in either mode; clamped to T, the
+    table's last entry).  inv_pen None: key = score.  inv_pen[n] = fp32(((5 + n) / 6) ** -alpha) (length_table).
+ 6. Selection: the first K of the candidates sorted by key descending, ties to the lower k1*K + k2 (a stable sort).
+ 7. Slot k with the chosen (k1, k2, w): parent[b,k] = k1; seq_lp'[b,k] = score (raw, not the key); seqs'[k,b,:t] = seqs[k1,b,:t],
+    seqs'[k,b,t] = w (positions behind t are left alone); tok[k*B+b] = w; finished'[b,k] = FREEZE ? (finished[b,k1] | (w == stop_id)) : 0;
+    length'[b,k] = len'.
+Mode EXTEND without penalty and mask is the reference's search (exp/gpv/models/gpv.py:209-362: finished hypotheses keep extending, no
+length normalisation); the only difference to GPV._beam_device's torch path is the last bit of lp (torch forms x - m - log s).
+Caller conditions: 1 <= K <= MAX_K, K <= V, T <= MAX_T; a mask leaves at least K finite entries per row; a NaN logit gives an undefined
+selection.
+"""
+import numpy as np
+
+EXTEND, FREEZE = 0, 1
+MODES = {'extend': EXTEND, 'freeze': FREEZE}
+MAX_K, MAX_T = 8, 64          # GPV_BEAM_MAX_K, GPV_BEAM_MAX_T
+LANES = 256                   # GPV_BEAM_LANES
+F32 = np.float32
+
+
+def length_table(T, alpha):
+    """inv_pen[n] = fp32(((5 + n) / 6) ** -alpha) for n = 0..T, computed in float64: the table both the host rule and the kernel read"""
+    n = np.arange(T + 1, dtype=np.float64)
+    return (((5.0 + n) / 6.0) ** (-float(alpha))).astype(np.float32)
+
+
+def n_chain(V):
+    """longest chain of dependent fp32 additions of the kernel's sum of exponentials (include/gpv_beam.h)"""
+    return -(-int(V) // LANES) + 6 + 3
+
+
+def check_extents(K, V, T, t=None):
+    if not 1 <= K <= MAX_K:
+        raise ValueError(f'beam: 1 <= beam size <= {MAX_K} is supported (GPV_BEAM_MAX_K), got {K}')
+    if K > V:
+        raise ValueError(f'beam: beam size {K} exceeds the vocabulary ({V})')
+    if not 2 <= T <= MAX_T:
+        raise ValueError(f'beam: 2 <= max_text_len <= {MAX_T} is supported (GPV_BEAM_MAX_T), got {T}')
+    if t is not None and not 0 <= t < T - 1:
+        raise ValueError(f'beam: step {t} outside 0 .. {T - 2}')
+
+
+def beam_step_host(logits, lse, seq_lp, seqs, finished, length, t, mode, pad_id, stop_id, inv_pen=None, vocab_mask=None):
+    """One step.  logits [K*B, V] (values exactly representable in fp32: fp32 or widened bf16), lse [K*B] fp32 (the device's, or any
+    log-sum-exp of the masked rows), seq_lp [B,K] fp32, seqs [K,B,T] int64, finished [B,K] 0/1, length [B,K] int.  Nothing is modified.
+    -> dict(parent [B,K] int32, tok [K*B] int64, seqs [K,B,T] int64, seq_lp [B,K] fp32, finished [B,K] int32, length [B,K] int32)"""
+    x = np.asarray(logits, dtype=F32)
+    K, B, T = seqs.shape
+    V = x.shape[1]
+    check_extents(K, V, T, t)
+    if x.shape[0] != K * B:
+        raise ValueError(f'beam: logits must have K*B = {K * B} rows, got {x.shape[0]}')
+    if mode not in (EXTEND, FREEZE):
+        raise ValueError(f'beam: mode must be EXTEND or FREEZE, got {mode!r}')
+    if vocab_mask is not None:
+        x = x + np.asarray(vocab_mask, dtype=F32)[None, :]                       # step 1
+    lse = np.asarray(lse, dtype=F32)
+    seq_lp = np.asarray(seq_lp, dtype=F32)
+    order = np.argsort(-x, axis=1, kind='stable')[:, :K]                         # step 3: K largest, ties to the lower v
+    out = {'parent': np.zeros((B, K), np.int32), 'tok': np.zeros(K * B, np.int64), 'seqs': np.array(seqs, dtype=np.int64),
+           'seq_lp': np.zeros((B, K), F32), 'finished': np.zeros((B, K), np.int32), 'length': np.zeros((B, K), np.int32)}
+    for b in range(B):
+        cands = []                                                               # (key, k1*K + k2, k1, w, score, len')
+        for k1 in range(K):
+            r = k1 * B + b
+            fin = bool(finished[b, k1])
+            ln = int(length[b, k1]) + (0 if fin else 1)
+            pen = None if inv_pen is None else F32(inv_pen[min(max(ln, 0), T)])
+            for k2 in range(K):
+                if mode == FREEZE and fin:
+                    if k2 > 0:
+                        continue
+                    w, score = pad_id, seq_lp[b, k1]
+                else:
+                    w = int(order[r, k2])
+                    lp = F32(x[r, w] - lse[r])                                   # one fp32 subtract
+                    score = F32(seq_lp[b, k1] + lp)                              # one fp32 add
+                    if t == 0 and k1 > 0:
+                        score = F32(-1e9)
+                key = score if pen is None else F32(score * pen)                 # one fp32 multiply
+                cands.append((key, k1 * K + k2, k1, w, score, ln))
+        cands.sort(key=lambda c: (-float(c[0]), c[1]))                           # step 6 (float(fp32) is exact, so is its negation)
+        for k, (_, _, k1, w, score, ln) in enumerate(cands[:K]):
+            out['parent'][b, k] = k1
+            out['seq_lp'][b, k] = score
+            out['seqs'][k, b, :t] = seqs[k1, b, :t]
+            out['seqs'][k, b, t] = w
+            out['tok'][k * B + b] = w
+            out['finished'][b, k] = int(mode == FREEZE and (bool(finished[b, k1]) or w == stop_id))
+            out['length'][b, k] = ln
+    return out
+
+
+def lse_host(logits, vocab_mask=None):
+    """a log-sum-exp of the masked rows for beam_search_host when no device is at hand: m + log(sum exp(x - m)) in float64, rounded to
+    fp32 (the device's own differs by its summation order, within the bound of tests/test_beam_gpu.py)"""
+    x = np.asarray(logits, dtype=F32)
+    if vocab_mask is not None:
+        x = x + np.asarray(vocab_mask, dtype=F32)[None, :]
+    m = x.max(axis=1).astype(np.float64)
+    return (m + np.log(np.exp(x.astype(np.float64) - m[:, None]).sum(axis=1))).astype(F32)
+
+
+def beam_search_host(step_logits_fn, B, K, T, cls_id, pad_id, stop_id, mode=EXTEND, alpha=0.0, vocab_mask=None):
+    """The chained search: step_logits_fn(t, tok [K,B,t+1] int64) -> logits [K*B, V] of the newest position (row k*B + b continues the
+    hypothesis in slot k of batch element b; tok[:, :, 0] = cls_id).  -> dict(seqs [K,B,T], seq_lp [B,K], finished, length, keys [B,K])"""
+    inv_pen = length_table(T, alpha) if alpha else None
+    seqs = np.zeros((K, B, T), np.int64)
+    seq_lp = np.zeros((B, K), F32)
+    finished = np.zeros((B, K), np.int32)
+    length = np.zeros((B, K), np.int32)
+    tok = np.full((K, B, 1), cls_id, np.int64)
+    bi = np.arange(B)
+    for t in range(T - 1):
+        logits = np.asarray(step_logits_fn(t, tok), dtype=F32)
+        o = beam_step_host(logits, lse_host(logits, vocab_mask), seq_lp, seqs, finished, length, t, mode, pad_id, stop_id,
+                           inv_pen=inv_pen, vocab_mask=vocab_mask)
+        par = o['parent'].T                                                       # [K,B]
+        tok = np.concatenate((tok[par, bi[None, :]], o['tok'].reshape(K, B, 1)), axis=-1)
+        seqs, seq_lp, finished, length = o['seqs'], o['seq_lp'], o['finished'], o['length']
+    keys = seq_lp if inv_pen is None else (seq_lp * inv_pen[np.clip(length, 0, T)]).astype(F32)
+    return {'seqs': seqs, 'seq_lp': seq_lp, 'finished': finished, 'length': length, 'keys': keys}

@@ -23,7 +23,7 @@ import re
 import numpy as np
 import torch
 
-from .inference import decode_outputs
+from .inference import beam_options, decode_outputs
 from .misc import NestedTensor, nested_tensor_from_tensor_list
 
 TASK_TO_ID = {'CocoVqa': 'question_id', 'CocoCaptioning': 'cap_id', 'CocoClassification': 'id', 'CocoDetection': 'id',
@@ -112,8 +112,10 @@ def boxes_to_h5py(npz_path, h5py_path):
 
 @torch.no_grad()
 def make_predictions(model, batches, eval_dir, task, subset='val', data_split='original_split', num_eval_batches=None,
-                     vocab_mask=None):
-    """compute_predictions.py:30-85; returns (predictions dict, json path, boxes path)"""
+                     vocab_mask=None, beam_size=None, beam=None):
+    """compute_predictions.py:30-85; returns (predictions dict, json path, boxes path).  beam_size / beam (added keys, as in
+    inference.predict: beam.impl, beam.finished, beam.length_penalty): answers by beam search instead of greedy decoding; a vocabulary
+    mask then needs beam.impl = device (GPV.forward_beam_search)"""
     dev = model.vision_token.device
     if vocab_mask is None and task == 'CocoClassification':
         vocab_mask = create_vocab_mask(model)[1]
@@ -128,7 +130,10 @@ def make_predictions(model, batches, eval_dir, task, subset='val', data_split='o
             break
         if not isinstance(imgs, NestedTensor):
             imgs = nested_tensor_from_tensor_list([x.to(dev) for x in imgs])
-        outputs = model(imgs, queries, None, vocab_mask=vocab_mask)
+        if beam_size:
+            outputs = model.forward_beam_search(imgs, queries, beam_size=beam_size, vocab_mask=vocab_mask, **beam_options(beam))
+        else:
+            outputs = model(imgs, queries, None, vocab_mask=vocab_mask)
         for sid, d in zip(sample_ids, decode_outputs(outputs, model, num_output_boxes=None)):
             predictions[sid] = {'answer': d['answer']}
             boxes_file.add(sid, d['boxes'], d['relevance'])

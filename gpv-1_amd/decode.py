@@ -165,6 +165,12 @@ class GreedyKVDecoder:
         for l in range(self.L):
             self.qkvc[l][:, :upto].copy_(self.qkvc[l][:, :upto].index_select(0, perm))
 
+    def reorder_device(self, parent, upto):
+        """beam search, device path: parent [B, K] int32 as gpv_beam_step wrote it -- sequence k*B + b continues the hypothesis of
+        slot parent[b, k] of the same b; the k | v columns of positions < upto of ALL layers move in one launch, in place"""
+        from . import hip_beam
+        hip_beam.reorder(self.qkvc, parent, upto)
+
     @torch.no_grad()
     def decode(self, memory, vocab_mask=None):
         """memory [B, Tm, D] -> (answer_logits [1,B,T,V] incl. the vocab mask like the reference, ids [B,T])"""

@@ -515,20 +515,52 @@ class GPV(nn.Module):
             logits = logits.float() + vocab_mask
         return logits.unsqueeze(0)
 
+    def _beam_options(self, impl, finished, length_penalty, vocab_mask):
+        """the beam options of one call: the argument, else cfg['beam'], else GPV_BEAM=device (impl only), else torch / extend / 0.0"""
+        bc = self.cfg.get('beam', None) or {}
+        if impl is None:
+            env = os.environ.get('GPV_BEAM', 'torch')      # device: beam search steps on the HIP path (hip_beam) when neither the call nor cfg beam.impl says otherwise
+            impl = bc.get('impl', None) or ('device' if env == 'device' else 'torch')
+        if finished is None:
+            finished = bc.get('finished', None) or 'extend'
+        if length_penalty is None:
+            length_penalty = bc.get('length_penalty', None) or 0.0
+        alpha = float(length_penalty)
+        if impl not in ('torch', 'device'):
+            raise ValueError(f"forward_beam_search: impl must be 'torch' or 'device', got {impl!r}")
+        if finished not in ('extend', 'freeze'):
+            raise ValueError(f"forward_beam_search: finished must be 'extend' or 'freeze', got {finished!r}")
+        if impl == 'torch':
+            # the torch path is the reference's search and nothing else: it is not taught the new rules
+            if finished == 'freeze':
+                raise ValueError("forward_beam_search: finished='freeze' needs impl='device' (the torch path keeps extending finished beams, as the reference does)")
+            if alpha != 0.0:
+                raise ValueError("forward_beam_search: a length penalty needs impl='device' (the torch path has no length normalisation, as the reference)")
+            if vocab_mask is not None:
+                raise ValueError("forward_beam_search: a vocabulary mask needs impl='device' (the torch path has none, as the reference)")
+        return impl, finished, alpha
+
     @torch.no_grad()
-    def forward_beam_search(self, images, queries, beam_size=1):
+    def forward_beam_search(self, images, queries, beam_size=1, vocab_mask=None, impl=None, finished=None, length_penalty=None):
         # (no GPV_OPT_PIPE_SMALL override here: the 320-row GEMMs of beam 5 x batch 64 want the small-M configurations -- 26.0 against 36.8 ms per batch)
         """gpv.py:209-362, quirks preserved (no length normalisation, finished beams keep extending --
-        the reference's `is True` test never fires --, last seqs slot never written, stable tie order)."""
+        the reference's `is True` test never fires --, last seqs slot never written, stable tie order).
+        impl='device' (or cfg beam.impl / GPV_BEAM=device) runs every step's selection and the cache reorder as two HIP launches
+        (hip_beam; the rule: gpv1_amd.beam) and is the only path that knows finished='freeze' (a hypothesis that emitted __stop__
+        keeps its score and is followed by __pad__), length_penalty (alpha of ((5 + len) / 6) ** alpha; the ranking key, not the
+        reported probability) and vocab_mask ([V] fp32 added to every row of logits)."""
+        impl, finished, alpha = self._beam_options(impl, finished, length_penalty, vocab_mask)
+        kw = dict(impl=impl, finished=finished, alpha=alpha)
         outputs = None
         if (not self.training and not torch.is_grad_enabled() and self.cfg.get('graph_inference', True)
                 and self.cfg.get('kv_decode', True)):
             # the whole beam search (encoder + 19 KV-cached steps with their top-k / sort / cache reordering) has static
             # shapes: one hipGraph, like the greedy path
             queries = self._host_tokenize(images, queries)
-            outputs = self._graphed(('beam', beam_size), lambda im, q, vm, qe: self._beam_device(im, q, beam_size), images, queries, None)
+            outputs = self._graphed(('beam', beam_size, impl, finished, alpha),
+                                    lambda im, q, vm, qe: self._beam_device(im, q, beam_size, vocab_mask=vm, **kw), images, queries, vocab_mask)
         if outputs is None:
-            outputs = self._beam_device(images, queries, beam_size)
+            outputs = self._beam_device(images, queries, beam_size, vocab_mask=vocab_mask, **kw)
         seqs, seq_lp = outputs.pop('_beam_seqs'), outputs.pop('_beam_lp')
         K, B, T = seqs.shape
         seqs_c, lp = seqs.cpu(), seq_lp.exp().cpu()
@@ -548,7 +580,7 @@ class GPV(nn.Module):
         outputs['answers'], outputs['answer_probs'] = answers, probs
         return outputs
 
-    def _beam_device(self, images, queries, beam_size):
+    def _beam_device(self, images, queries, beam_size, vocab_mask=None, impl='torch', finished='extend', alpha=0.0):
         """device part of the beam search: outputs dict + '_beam_seqs' [K,B,T] + '_beam_lp' [B,K] (no host round trip)"""
         graphed = isinstance(queries, (tuple, list)) and len(queries) == 2 and all(torch.is_tensor(q) for q in queries) and \
             hasattr(images, 'tensors') and images.tensors.is_cuda and torch.cuda.is_current_stream_capturing()
@@ -570,6 +602,11 @@ class GPV(nn.Module):
                 kv = self._kvdec[key] = GreedyKVDecoder(self, K * B, memK.shape[1], use_graphs=False)
             kv.memory.copy_(memK.reshape(K * B * memK.shape[1], -1))
             kv._prepare()
+        if impl == 'device':
+            if kv is None:
+                raise RuntimeError("forward_beam_search: impl='device' needs the KV-cached decoder (eval mode, no grad, cfg kv_decode); "
+                                   "there is no fallback to the torch path")
+            return self._beam_steps_device(outputs, kv, B, K, T, vocab_mask, finished, alpha)
         for t in range(T - 1):
             if kv is not None:
                 kv.tok.copy_(tok[:, :, -1].reshape(K * B))
@@ -594,6 +631,36 @@ class GPV(nn.Module):
             if kv is not None:                                                     # slot (k, b) continues parent (k1[b,k], b)
                 kv.reorder((k1.t() * B + bi.t()).reshape(K * B), t + 1)
         outputs['_beam_seqs'], outputs['_beam_lp'] = seqs, seq_lp
+        return outputs
+
+    def _beam_steps_device(self, outputs, kv, B, K, T, vocab_mask, finished, alpha):
+        """the T - 1 steps of the device path: decoder core, gpv_beam_step (writes the next tokens straight into kv.tok), gpv_beam_reorder
+        -- two launches per token beside the decoder's, no allocation inside the loop"""
+        from . import beam as rule, hip_beam
+        rule.check_extents(K, len(self.vocab), T)
+        dev = kv.tok.device
+        inv_pen = None
+        if alpha != 0.0:
+            tables = self.__dict__.setdefault('_beam_tables', {})            # (filled by the warm-up runs: a capture finds it on the device)
+            inv_pen = tables.get((T, alpha, str(dev)))
+            if inv_pen is None:
+                inv_pen = tables[(T, alpha, str(dev))] = torch.from_numpy(rule.length_table(T, alpha)).to(dev)
+        if vocab_mask is not None:
+            vocab_mask = vocab_mask.to(device=dev, dtype=torch.float32).contiguous()
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+        seq_lp = torch.zeros(B, K, device=dev)
+        seqs = torch.zeros(K, B, T, dtype=torch.long, device=dev)
+        lse = torch.zeros(K * B, device=dev)
+        parent, fin, length = i32(B, K), i32(B, K), i32(B, K)
+        kv.tok.fill_(self.word_to_idx['__cls__'])
+        mode, pad, stop = rule.MODES[finished], self.word_to_idx['__pad__'], self.word_to_idx['__stop__']
+        for t in range(T - 1):
+            hip_beam.step(kv._step_core(t), lse, seq_lp, seqs, kv.tok, parent, fin, length, t, mode, pad, stop,
+                          inv_pen=inv_pen, vocab_mask=vocab_mask)
+            if t + 1 < T - 1:                                                  # (nothing reads the caches after the last step)
+                kv.reorder_device(parent, t + 1)
+        outputs['_beam_seqs'], outputs['_beam_lp'] = seqs, seq_lp
+        outputs['beam_lengths'], outputs['beam_finished'] = length, fin
         return outputs
 
     def encode_answers(self, targets):

@@ -1,0 +1,113 @@
+"""ctypes binding of libgpv_beam.so (C ABI in include/gpv_beam.h): the beam search step and the KV-cache reorder on the device.
+
+A sixth library next to libgpv_hip.so (``hip.EXPORTS``), libgpv_eval.so, libgpv_cap.so, libgpv_match.so and libgpv_health.so: those
+export lists are pinned.  Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.  Nothing
+here synchronises or allocates: both calls are capturable.  The rule is stated in ``gpv1_amd.beam``.
+"""
+import ctypes as C
+import os
+
+import torch
+
+from . import beam as rule
+from .hip import _chk, _stream
+
+EXPORTS = ['gpv_beam_reorder', 'gpv_beam_step']
+MAX_K, MAX_T, MAX_LAYERS = rule.MAX_K, rule.MAX_T, 8      # GPV_BEAM_MAX_K, GPV_BEAM_MAX_T, GPV_BEAM_MAX_LAYERS
+_DTYPES = {torch.bfloat16: 0, torch.float32: 1}           # GPV_BEAM_BF16, GPV_BEAM_F32
+_LIB = None
+_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libgpv_beam.so')
+
+
+class BeamArgs(C.Structure):
+    _fields_ = [('logits', C.c_void_p), ('pitch', C.c_int64), ('vocab_mask', C.c_void_p), ('inv_pen', C.c_void_p), ('lse', C.c_void_p),
+                ('seq_lp', C.c_void_p), ('seqs', C.c_void_p), ('tok', C.c_void_p), ('parent', C.c_void_p), ('finished', C.c_void_p),
+                ('length', C.c_void_p), ('B', C.c_int), ('K', C.c_int), ('V', C.c_int), ('T', C.c_int), ('t', C.c_int),
+                ('mode', C.c_int), ('pad_id', C.c_int), ('stop_id', C.c_int), ('dtype', C.c_int)]
+
+
+class ReorderArgs(C.Structure):
+    _fields_ = [('cache', C.c_void_p * MAX_LAYERS), ('parent', C.c_void_p), ('L', C.c_int), ('B', C.c_int), ('K', C.c_int),
+                ('T', C.c_int), ('D', C.c_int), ('upto', C.c_int), ('dtype', C.c_int)]
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        if not os.path.exists(_LIB_PATH):
+            raise RuntimeError(
+                f'gpv1_amd: beam search kernel library not found at {_LIB_PATH}. Build it with '
+                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
+                f'There is no CPU/eager fallback by design.')
+        _LIB = C.CDLL(_LIB_PATH)
+        _LIB.gpv_beam_step.restype = C.c_int
+        _LIB.gpv_beam_step.argtypes = [C.POINTER(BeamArgs), C.c_void_p]
+        _LIB.gpv_beam_reorder.restype = C.c_int
+        _LIB.gpv_beam_reorder.argtypes = [C.POINTER(ReorderArgs), C.c_void_p]
+    return _LIB
+
+
+def _want(name, t, dtype, shape):
+    if not t.is_cuda:
+        raise RuntimeError(f'gpv1_amd: hip_beam: {name} must live on the GPU (no CPU fallback exists for the device beam step)')
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f'hip_beam: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
+    return t.data_ptr()
+
+
+def step(logits, lse, seq_lp, seqs, tok, parent, finished, length, t, mode, pad_id, stop_id, inv_pen=None, vocab_mask=None):
+    """gpv_beam_step on the current stream: one launch, no sync, everything in place.  logits [K*B, V] bf16 / fp32 with unit column
+    stride (any row pitch >= V: a view of the decoder's [K*B, T, V] buffer), lse [K*B] fp32 out, seq_lp [B,K] fp32, seqs [K,B,T] int64,
+    tok [K*B] int64 out, parent [B,K] int32 out, finished / length [B,K] int32; inv_pen [T+1] fp32 or None, vocab_mask [V] fp32 or None."""
+    if not logits.is_cuda:
+        raise RuntimeError('gpv1_amd: hip_beam: logits must live on the GPU (no CPU fallback exists for the device beam step)')
+    if logits.dim() != 2 or seqs.dim() != 3:
+        raise ValueError(f'hip_beam.step: logits must be [K*B, V] and seqs [K,B,T], got {tuple(logits.shape)} {tuple(seqs.shape)}')
+    K, B, T = seqs.shape
+    R, V = logits.shape
+    rule.check_extents(K, V, T, t)
+    if R != K * B:
+        raise ValueError(f'hip_beam.step: logits must have K*B = {K * B} rows, got {R}')
+    if logits.dtype not in _DTYPES:
+        raise ValueError(f'hip_beam.step: logits must be bfloat16 or float32, got {logits.dtype}')
+    if logits.stride(1) != 1 or (R > 1 and logits.stride(0) < V):
+        raise ValueError(f'hip_beam.step: logits need unit column stride and a row pitch >= V, got strides {tuple(logits.stride())}')
+    if mode not in (rule.EXTEND, rule.FREEZE):
+        raise ValueError(f'hip_beam.step: mode must be EXTEND (0) or FREEZE (1), got {mode!r}')
+    if not (0 <= pad_id < V and 0 <= stop_id < V):
+        raise ValueError(f'hip_beam.step: pad_id / stop_id must lie in the vocabulary, got {pad_id} / {stop_id} of {V}')
+    a = BeamArgs(logits=logits.data_ptr(), pitch=logits.stride(0) if R > 1 else V,
+                 vocab_mask=None if vocab_mask is None else _want('vocab_mask', vocab_mask, torch.float32, (V,)),
+                 inv_pen=None if inv_pen is None else _want('inv_pen', inv_pen, torch.float32, (T + 1,)),
+                 lse=_want('lse', lse, torch.float32, (R,)), seq_lp=_want('seq_lp', seq_lp, torch.float32, (B, K)),
+                 seqs=_want('seqs', seqs, torch.int64, (K, B, T)), tok=_want('tok', tok, torch.int64, (R,)),
+                 parent=_want('parent', parent, torch.int32, (B, K)), finished=_want('finished', finished, torch.int32, (B, K)),
+                 length=_want('length', length, torch.int32, (B, K)), B=B, K=K, V=V, T=T, t=t, mode=mode, pad_id=pad_id,
+                 stop_id=stop_id, dtype=_DTYPES[logits.dtype])
+    _chk(lib().gpv_beam_step(C.byref(a), _stream()), 'gpv_beam_step')
+
+
+def reorder(caches, parent, upto):
+    """gpv_beam_reorder on the current stream: one launch for all layers, in place, no sync.  caches: L contiguous [K*B, T, 3D] tensors
+    of one dtype (q | k | v columns), parent [B,K] int32: for positions < upto and the k | v columns row k*B+b becomes old row
+    parent[b,k]*B+b."""
+    B, K = parent.shape
+    L = len(caches)
+    if not 1 <= L <= MAX_LAYERS:
+        raise ValueError(f'hip_beam.reorder: 1 .. {MAX_LAYERS} layers per call (GPV_BEAM_MAX_LAYERS), got {L}')
+    if not 1 <= K <= MAX_K:
+        raise ValueError(f'hip_beam.reorder: 1 <= beam size <= {MAX_K} is supported (GPV_BEAM_MAX_K), got {K}')
+    c0 = caches[0]
+    if c0.dim() != 3 or c0.shape[0] != K * B or c0.shape[2] % 3 != 0 or c0.dtype not in _DTYPES:
+        raise ValueError(f'hip_beam.reorder: caches must be [K*B = {K * B}, T, 3D] bfloat16 or float32, got {c0.dtype} {tuple(c0.shape)}')
+    T, D = c0.shape[1], c0.shape[2] // 3
+    if not 1 <= upto <= T:
+        raise ValueError(f'hip_beam.reorder: upto must lie in 1 .. T = {T}, got {upto}')
+    if (D * c0.element_size()) % 16 != 0:
+        raise ValueError(f'hip_beam.reorder: the hidden size ({D} x {c0.element_size()} bytes) must be a multiple of 16 bytes')
+    a = ReorderArgs(parent=_want('parent', parent, torch.int32, (B, K)), L=L, B=B, K=K, T=T, D=D, upto=upto, dtype=_DTYPES[c0.dtype])
+    for l, c in enumerate(caches):
+        a.cache[l] = _want(f'caches[{l}]', c, c0.dtype, c0.shape)
+        if a.cache[l] % 16 != 0:
+            raise ValueError(f'hip_beam.reorder: caches[{l}] is not 16-byte aligned')
+    _chk(lib().gpv_beam_reorder(C.byref(a), _stream()), 'gpv_beam_reorder')

@@ -11,6 +11,7 @@ punctuation-attachment rules (a join that glues ``, . ! ? ; : ' n't 's %`` to th
 
 usage: python -m gpv1_amd.inference [--config some.yaml] ckpt=... inputs.img=img.npy inputs.query="what is this?"
                                       [beam_size=5] [num_output_boxes=5]
+                                      [beam.impl=device] [beam.finished=freeze] [beam.length_penalty=0.6]
 """
 import argparse
 import os
@@ -111,8 +112,16 @@ def decode_outputs(outputs, model, num_output_boxes=None):
     return decoded
 
 
+def beam_options(beam):
+    """the `beam` group of a config (added keys beam.impl / beam.finished / beam.length_penalty) as forward_beam_search's keywords;
+    a key that is absent is left to the model's own defaults (its cfg['beam'], GPV_BEAM)"""
+    beam = beam or {}
+    names = {'impl': 'impl', 'finished': 'finished', 'length_penalty': 'length_penalty'}
+    return {kw: beam.get(k) for k, kw in names.items() if beam.get(k, None) is not None}
+
+
 @torch.no_grad()
-def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=None):
+def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=None, beam=None):
     """images: list of arrays/tensors (see preprocess_image); queries: list[str] or (ids, mask) tensors;
     size: (H, W) to resize HxWx3 arrays to first (the data loader's 480x640), None = as they are (inference.py).  Any image size
     runs: the batch is padded to its largest image and the encoder attends over ceil(H / 32) ceil(W / 32) tokens (850 for
@@ -122,7 +131,7 @@ def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=
         images = [resize_image(i, size) if not torch.is_tensor(i) else i for i in images]
     imgs = nested_tensor_from_tensor_list([preprocess_image(i).to(dev) for i in images])
     if beam_size:
-        out = model.forward_beam_search(imgs, queries, beam_size=beam_size)
+        out = model.forward_beam_search(imgs, queries, beam_size=beam_size, **beam_options(beam))
     else:
         out = model(imgs, queries, None)
     return decode_outputs(out, model, num_output_boxes)
@@ -133,12 +142,13 @@ def main(argv=None):
     ap.add_argument('--config', default=None, help='YAML file (e.g. the reference configs/exp/gpv.yaml); default: gpv1_amd.default_config')
     ap.add_argument('overrides', nargs='*')
     args = ap.parse_args(argv)
-    # ckpt= inputs.img= inputs.query= beam_size= are added keys
+    # ckpt= inputs.img= inputs.query= beam_size= beam.impl= beam.finished= beam.length_penalty= are added keys
     cfg = load_config(args.config, args.overrides, strict=False) if args.config else from_dict(default_tree(), args.overrides, strict=False)
     model = GPV(cfg.model).cuda().eval()
     load_model_state(model, cfg.get('ckpt', cfg.eval.ckpt), map_location='cuda:0')
     img = np.load(cfg.inputs.img)
-    pred = predict(model, [img], [cfg.inputs.query], beam_size=cfg.get('beam_size'), num_output_boxes=cfg.get('num_output_boxes', 5))[0]
+    pred = predict(model, [img], [cfg.inputs.query], beam_size=cfg.get('beam_size'), num_output_boxes=cfg.get('num_output_boxes', 5),
+                   beam=cfg.get('beam'))[0]
     for k, v in pred.items():
         print('-' * 80)
         print(k)

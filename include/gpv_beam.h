@@ -1,0 +1,91 @@
+/* C ABI of libgpv_beam.so: one beam search step on the device and the KV-cache reorder of all decoder layers
+ * (gpv-1_amd/csrc/beam_step.hip).  The host statement of the same rule is gpv1_amd.beam.beam_step_host.
+ *
+ * A library of its own beside libgpv_hip.so, libgpv_eval.so, libgpv_cap.so, libgpv_match.so and libgpv_health.so: those five
+ * export lists are pinned.  Every function takes plain device pointers, returns a hipError_t as int (0 = ok), launches on
+ * `stream`, never synchronises, allocates nothing and keeps no global state (capturable).  Anything outside the stated extents
+ * returns hipErrorInvalidValue before a launch.
+ *
+ * THE RULE.  Step t (0 <= t < T-1), batch element b, parent k1 = 0..K-1, logits row r = k1*B + b:
+ *  1. x_v = fp32(logit[r, v]) + vocab_mask[v]: one fp32 add; no add when the mask is absent.
+ *  2. lse_r = m + logf(sum_v expf(x_v - m)), m = max_v x_v, fp32.  The summation order is the kernel's own (below); lse is an
+ *     OUTPUT of the step ([K*B] fp32) and an INPUT of the host rule, so no transcendental is evaluated on both sides and
+ *     everything below is bit-exact.
+ *  3. The row's candidates are its K largest x_v, ties to the lower v; k2 is the rank.  lp = x_v - lse_r: one fp32 subtract.
+ *  4. score(k1,k2) = seq_lp[b,k1] + lp: one fp32 add.  t == 0 and k1 > 0: score = -1e9 exactly.  Mode FREEZE with
+ *     finished[b,k1] set: the parent has exactly one candidate, k2 = 0, token pad_id, score = seq_lp[b,k1] unchanged; its other
+ *     candidates do not exist.
+ *  5. key = score * inv_pen[len']: one fp32 multiply, len' = length[b,k1] + (finished[b,k1] ? 0 : 1) (in either mode; clamped to
+ *     T, the table's last entry).  inv_pen == NULL: key = score.  inv_pen[n] = fp32(((5 + n) / 6) ** -alpha), n = 0..T, computed
+ *     once in float64 on the host (gpv1_amd.beam.length_table); the host rule and the kernel read the same table.
+ *  6. Selection: the first K of the candidates sorted by key descending, ties to the lower k1*K + k2 (a stable sort).
+ *  7. Slot k with the chosen (k1, k2, w): parent[b,k] = k1; seq_lp'[b,k] = score (raw, not the key);
+ *     seqs'[k,b,:t] = seqs[k1,b,:t], seqs'[k,b,t] = w (positions behind t are left alone); tok[k*B+b] = w;
+ *     finished'[b,k] = FREEZE ? (finished[b,k1] | (w == stop_id)) : 0; length'[b,k] = len'.
+ * Mode EXTEND without penalty and mask is the reference's search (finished hypotheses keep extending, no normalisation).
+ * Caller conditions: 1 <= K <= GPV_BEAM_MAX_K, K <= V, T <= GPV_BEAM_MAX_T; a mask leaves at least K finite entries per row; a
+ * NaN logit gives an undefined selection (every index written stays inside its array; no loop bound depends on the data).
+ *
+ * THE SUM OF STEP 2.  256 lanes; lane l adds expf(x_v - m) for v = l, l + 256, l + 512, ... in ascending v onto 0.f, the 64 lanes
+ * of a wave are folded by xor butterflies (32, 16, 8, 4, 2, 1), the four wave sums are added one after the other in wave order.
+ * The longest chain of dependent fp32 additions is therefore  n_chain(V) = ceil(V / 256) + 6 + 3. */
+#ifndef GPV_BEAM_H
+#define GPV_BEAM_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define GPV_BEAM_MAX_K 8        /* beams per batch element */
+#define GPV_BEAM_MAX_T 64       /* max_text_len */
+#define GPV_BEAM_MAX_LAYERS 8   /* decoder layers of one gpv_beam_reorder call */
+#define GPV_BEAM_LANES 256      /* threads of a gpv_beam_step workgroup: the stride of the sum of step 2 */
+
+#define GPV_BEAM_EXTEND 0       /* finished hypotheses keep extending (the reference) */
+#define GPV_BEAM_FREEZE 1       /* a hypothesis that emitted stop_id keeps its score and is followed by pad_id */
+
+#define GPV_BEAM_BF16 0         /* dtype codes, the values of GPV_BF16 / GPV_F32 in gpv_hip.h */
+#define GPV_BEAM_F32 1
+
+typedef struct gpv_beam_args {
+  const void* logits;           /* [K*B, V] bf16 or fp32, row r at logits + r * pitch elements */
+  int64_t pitch;                /* row pitch in elements, >= V (the decoder writes logits[:, t] with pitch T*V) */
+  const float* vocab_mask;      /* [V] fp32 added to every row, or NULL */
+  const float* inv_pen;         /* [T+1] fp32 length-penalty table, or NULL */
+  float* lse;                   /* [K*B] out */
+  float* seq_lp;                /* [B,K] in / out */
+  int64_t* seqs;                /* [K,B,T] in / out */
+  int64_t* tok;                 /* [K*B] out: the decoder's next input tokens */
+  int* parent;                  /* [B,K] out */
+  int* finished;                /* [B,K] in / out, 0 or 1 */
+  int* length;                  /* [B,K] in / out */
+  int B, K, V, T, t;
+  int mode;                     /* GPV_BEAM_EXTEND / GPV_BEAM_FREEZE */
+  int pad_id, stop_id;          /* in [0, V) */
+  int dtype;                    /* of logits: GPV_BEAM_BF16 / GPV_BEAM_F32 */
+} gpv_beam_args;
+
+/* One launch, one workgroup of GPV_BEAM_LANES threads per batch element.  Per row every thread keeps a sorted top-K list over
+ * its strided elements, the workgroup pops K winners with (value, index) arg-max reductions (the first is the row maximum) and
+ * sums the exponentials; the K*K candidates (one wave) are ranked by counting how many candidates beat each one; the workgroup
+ * stages the K seqs rows of its b in LDS before it writes them back, so seqs, seq_lp, finished and length are updated in place.
+ * Every load is from a clamped index and padded at use.  B = 0: nothing is launched. */
+int gpv_beam_step(const gpv_beam_args* a, void* stream);
+
+typedef struct gpv_beam_reorder_args {
+  void* cache[GPV_BEAM_MAX_LAYERS];   /* L caches [K*B, T, 3*D] (q | k | v columns), 16-byte aligned */
+  const int* parent;                  /* [B,K] of gpv_beam_step (values outside 0..K-1 are clamped) */
+  int L, B, K, T, D;
+  int upto;                           /* positions < upto move, 1 <= upto <= T */
+  int dtype;                          /* GPV_BEAM_BF16 / GPV_BEAM_F32; D * element size must be a multiple of 16 */
+} gpv_beam_reorder_args;
+
+/* One launch for all L layers: for positions < upto and the k | v columns, row k*B+b becomes old row parent[b,k]*B+b.  A thread
+ * owns one (layer, b, position, 16-byte column vector), reads its K values and then writes its K values: in place, no scratch.
+ * Positions >= upto and the q columns are not touched. */
+int gpv_beam_reorder(const gpv_beam_reorder_args* a, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
