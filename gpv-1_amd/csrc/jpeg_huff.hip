@@ -1,0 +1,205 @@
+// libgpv_huff.so: the Huffman stream of baseline JPEG files decoded on the device (include/gpv_huff.h states the rule and the ABI,
+// gpv1_amd.jpeg_entropy is the host statement, jpeg_huff_host.h holds the host pass and the symbol walk).
+//
+// One workgroup of 1024 threads serves one image, one launch serves the batch:
+//   0. the descriptor (geometry + the six tables, 8.7 KB) is copied to LDS; the coefficients are zeroed with 16-byte stores
+//   1. pass 0: thread t walks subsequences t, t + 1024, ... from bit i*S in state (0, 0); end states go to the workspace
+//   2. pass k: a subsequence whose predecessor's end state changed is walked again from that state.  The states are double-buffered
+//      (a pass reads what the pass before left, never what a neighbour is writing), a flag in LDS (one per pass parity) and two barriers decide whether
+//      another pass follows.  At most n_sub passes.
+//   3. blocks finished per subsequence -> exclusive prefix (a chunk per thread, the chunk sums scanned in LDS)
+//   4. write pass: every subsequence once more, now storing AC values and DC differences
+//   5. DC: a chunk of MCUs per thread, per-component sums through LDS, running sums written back as int16
+// Loop bounds: passes <= n_sub, symbols per walk <= S, strides over n_sub and the MCU count -- all from arguments and descriptor
+// fields, none from decoded data.  Loads go to clamped indices.  Several workgroups per image: left for later.
+#include <hip/hip_runtime.h>
+#include "jpeg_huff_host.h"
+
+namespace {
+
+using namespace gpv_huff_host;
+constexpr int LANES = GPV_HUFF_LANES;
+
+static_assert(sizeof(gpv_huff_desc) % 8 == 0, "the descriptor is copied to LDS in 8-byte words");
+
+__device__ __forceinline__ uint64_t pack(uint32_t p, int c, int z) { return ((uint64_t)p << 16) | ((uint64_t)(c & 255) << 8) | (uint64_t)(z & 255); }
+
+// exclusive prefix of v over the workgroup (Hillis-Steele in LDS, log2(LANES) steps); total = the sum of all
+__device__ __forceinline__ uint32_t block_scan(uint32_t* s, int tid, uint32_t v, uint32_t& total) {
+  s[tid] = v;
+  __syncthreads();
+  for (int off = 1; off < LANES; off <<= 1) {
+    const uint32_t add = tid >= off ? s[tid - off] : 0u;
+    __syncthreads();
+    s[tid] += add;
+    __syncthreads();
+  }
+  total = s[LANES - 1];
+  const uint32_t incl = s[tid];
+  __syncthreads();
+  return incl - v;
+}
+
+__global__ __launch_bounds__(LANES) void huff_decode_kernel(const gpv_huff_desc* __restrict__ descs, int S, int M, uint32_t max_nbits,
+                                                            unsigned char* __restrict__ ws) {
+  __shared__ gpv_huff_desc d;
+  __shared__ uint32_t s_sum[3][LANES];
+  __shared__ int s_flag[2], s_err;
+  const int tid = threadIdx.x;
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(descs + blockIdx.x);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&d);
+    for (int i = tid; i < (int)(sizeof(gpv_huff_desc) / 8); i += LANES) dst[i] = src[i];
+    if (tid == 0) { s_flag[0] = s_flag[1] = 0; s_err = 0; }
+  }
+  __syncthreads();
+  const uint32_t nbits = (uint32_t)d.nbits;
+  const int nwords = d.stream_cap / 4;
+  const int bpm = d.blocks_per_mcu;
+  const int64_t nmcu64 = (int64_t)d.mcus_x * d.mcus_y;
+  // a descriptor outside the extents of the call: nothing is decoded (uniform over the workgroup)
+  if (d.nbits < 0 || nbits > max_nbits || nwords < 4 || (int64_t)nwords * 32 < (int64_t)nbits + 64 || bpm < 1 || bpm > 6 || d.ncomp < 1 ||
+      d.ncomp > 3 || d.mcus_x < 1 || d.mcus_y < 1 || nmcu64 * bpm != d.nblocks || d.coef_count < 64 || (d.coef_count & 63) ||
+      (reinterpret_cast<uintptr_t>(d.coefs) & 15) || (reinterpret_cast<uintptr_t>(d.stream) & 15)) {
+    if (tid == 0) { d.status[0] = GPV_HUFF_ERR_EXTENT; d.status[1] = 0; }
+    return;
+  }
+  const int nmcu = (int)nmcu64;
+  int n_sub = (int)((nbits + (uint32_t)S - 1) / (uint32_t)S);
+  n_sub = n_sub < 1 ? 1 : (n_sub > M ? M : n_sub);       // (n_sub <= M follows from nbits <= max_nbits)
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(d.stream);
+  short* coefs = d.coefs;
+  unsigned char* my = ws + (size_t)blockIdx.x * (size_t)M * GPV_HUFF_WS_PER_SUB;
+  uint64_t* st[2] = {reinterpret_cast<uint64_t*>(my), reinterpret_cast<uint64_t*>(my) + M};
+  uint32_t* u32 = reinterpret_cast<uint32_t*>(my + (size_t)M * 16);
+  uint32_t* cnt[2] = {u32, u32 + M};
+  uint32_t* chg[2] = {u32 + 2 * (size_t)M, u32 + 3 * (size_t)M};
+  uint32_t* first = u32 + 4 * (size_t)M;
+
+  {                                                       // 0. zero the coefficients
+    uint4* z4 = reinterpret_cast<uint4*>(coefs);
+    const int64_t n16 = d.coef_count / 8;
+    for (int64_t i = tid; i < n16; i += LANES) z4[i] = make_uint4(0, 0, 0, 0);
+  }
+
+  int cur = 0, passes = 0;
+  for (int k = 0; k < n_sub; ++k) {                       // 1. / 2.
+    const int nxt = cur ^ 1;
+    int any = 0;
+    for (int i = tid; i < n_sub; i += LANES) {
+      const uint32_t hi = (uint32_t)(i + 1) * (uint32_t)S;
+      const uint32_t limit = hi < nbits ? hi : nbits;
+      uint64_t s_new;
+      uint32_t c_new, changed;
+      bool redo = k == 0;
+      uint32_t p = (uint32_t)i * (uint32_t)S;
+      p = p < nbits ? p : nbits;
+      int c = 0, z = 0;
+      if (k > 0 && i > 0 && chg[cur][i - 1]) {
+        const uint64_t s = st[cur][i - 1];
+        p = (uint32_t)(s >> 16); c = (int)((s >> 8) & 255); z = (int)(s & 255);
+        redo = true;
+      }
+      if (redo) {
+        int n = 0, err = 0;
+        walk<false>(d, words, nwords, p, c, z, limit, S, n, nullptr, 0, err);
+        s_new = pack(p, c, z);
+        c_new = (uint32_t)n;
+        changed = k == 0 ? 1u : (s_new != st[cur][i] ? 1u : 0u);
+      } else {
+        s_new = st[cur][i]; c_new = cnt[cur][i]; changed = 0;
+      }
+      st[nxt][i] = s_new; cnt[nxt][i] = c_new; chg[nxt][i] = changed;
+      if (changed && i < n_sub - 1) any = 1;
+    }
+    if (any) s_flag[k & 1] = 1;
+    __syncthreads();                                      // the states of this pass are written, its flag is complete
+    const int again = s_flag[k & 1];
+    if (tid == 0) s_flag[(k + 1) & 1] = 0;                // the next pass's flag: last read before the barrier above, next set behind the one below
+    cur = nxt;
+    ++passes;
+    __syncthreads();
+    if (!again) break;                                    // (uniform)
+  }
+  __syncthreads();
+
+  {                                                       // 3. exclusive prefix of the blocks finished
+    const int chunk = (n_sub + LANES - 1) / LANES;
+    const int lo = tid * chunk < n_sub ? tid * chunk : n_sub, hi = lo + chunk < n_sub ? lo + chunk : n_sub;
+    uint32_t sum = 0;
+    for (int i = lo; i < hi; ++i) sum += cnt[cur][i];
+    uint32_t total = 0;
+    uint32_t run = block_scan(s_sum[0], tid, sum, total);
+    for (int i = lo; i < hi; ++i) { first[i] = run; run += cnt[cur][i]; }
+    if (tid == 0 && total < (uint32_t)d.nblocks) atomicOr(&s_err, GPV_HUFF_ERR_SHORT);
+    __syncthreads();
+  }
+
+  {                                                       // 4. the write pass
+    int err = 0;
+    for (int i = tid; i < n_sub; i += LANES) {
+      const uint32_t hi = (uint32_t)(i + 1) * (uint32_t)S;
+      const uint32_t limit = hi < nbits ? hi : nbits;
+      uint32_t p = 0;
+      int c = 0, z = 0, n = 0;
+      if (i > 0) { const uint64_t s = st[cur][i - 1]; p = (uint32_t)(s >> 16); c = (int)((s >> 8) & 255); z = (int)(s & 255); }
+      const uint32_t b0 = first[i];
+      walk<true>(d, words, nwords, p, c, z, limit, S, n, coefs, b0 < 0x40000000u ? (int)b0 : 0x40000000, err);
+    }
+    if (err) atomicOr(&s_err, err);
+    __syncthreads();
+  }
+
+  {                                                       // 5. DC differences -> values, per component in scan order
+    const int chunk = (nmcu + LANES - 1) / LANES;
+    const int lo = tid * chunk < nmcu ? tid * chunk : nmcu, hi = lo + chunk < nmcu ? lo + chunk : nmcu;
+    uint32_t sum[3] = {0, 0, 0};
+    for (int m = lo; m < hi; ++m)
+      for (int j = 0; j < bpm; ++j) {
+        const int c = d.blk_comp[j] < 3 ? d.blk_comp[j] : 2;
+        sum[c] += (uint32_t)(int)coefs[block_address(d, bpm, m * bpm + j)];
+      }
+    uint32_t run[3], total;
+    for (int c = 0; c < 3; ++c) run[c] = block_scan(s_sum[c], tid, sum[c], total);
+    for (int m = lo; m < hi; ++m)
+      for (int j = 0; j < bpm; ++j) {
+        const int c = d.blk_comp[j] < 3 ? d.blk_comp[j] : 2;
+        const int64_t a = block_address(d, bpm, m * bpm + j);
+        run[c] += (uint32_t)(int)coefs[a];
+        coefs[a] = (short)(int)run[c];
+      }
+  }
+  __syncthreads();
+  if (tid == 0) { d.status[0] = s_err; d.status[1] = passes; }
+}
+
+bool subseq_ok(int S) { return S >= GPV_HUFF_MIN_S && S <= GPV_HUFF_MAX_S && S % 32 == 0; }
+constexpr int64_t kMaxBits = (int64_t)GPV_HUFF_MAX_STREAM * 8;
+
+}  // namespace
+
+extern "C" int gpv_huff_prepare(const unsigned char* data, int64_t nbytes, gpv_jpeg_info* info, gpv_huff_desc* desc, unsigned char* out,
+                                int64_t out_capacity, int64_t* stream_cap, int* route) {
+  static thread_local gpv_huff_host::Tables tabs;
+  return gpv_huff_host::prepare(data, nbytes, info, desc, out, out_capacity, stream_cap, route, tabs);
+}
+
+extern "C" int gpv_huff_workspace_bytes(int B, int subseq_bits, int64_t max_nbits, int64_t* bytes) {
+  if (!bytes || B <= 0 || !subseq_ok(subseq_bits) || max_nbits < 0 || max_nbits > kMaxBits) return (int)hipErrorInvalidValue;
+  const int64_t M = max_nbits / subseq_bits + 1;
+  *bytes = (int64_t)B * M * GPV_HUFF_WS_PER_SUB;
+  return 0;
+}
+
+extern "C" int gpv_huff_decode(const gpv_huff_desc* descs, int B, int subseq_bits, int64_t max_nbits, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  int64_t need = 0;
+  if (!descs || !workspace || gpv_huff_workspace_bytes(B, subseq_bits, max_nbits, &need) || workspace_bytes < need ||
+      (reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(descs) & 7))
+    return (int)hipErrorInvalidValue;
+  const int M = (int)(max_nbits / subseq_bits + 1);
+  hipLaunchKernelGGL(huff_decode_kernel, dim3((unsigned)B), dim3(LANES), 0, reinterpret_cast<hipStream_t>(stream), descs, subseq_bits, M,
+                     (uint32_t)max_nbits, static_cast<unsigned char*>(workspace));
+  const hipError_t e = hipGetLastError();
+  return (int)e;
+}

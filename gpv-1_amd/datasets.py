@@ -211,12 +211,15 @@ class DeviceLoader:
     thread grows the slot.  Upload, decode and image pipeline of batch n + 1 are issued (asynchronously) by the main thread when
     the caller asks for that batch.  prefetch=0 is the same code without the thread.  device=None: the host half only (host_batches)."""
 
-    def __init__(self, dataset, batch_size, device='cuda', size=None, threads=8, prefetch=1):
+    def __init__(self, dataset, batch_size, device='cuda', size=None, threads=8, prefetch=1, entropy='host', subseq_bits=1024):
+        """entropy / subseq_bits: DeviceJpegDecoder's -- 'device' moves the Huffman walk to the GPU; the worker's half (gpv_huff_prepare)
+        still makes no HIP call"""
         from .jpeg import DeviceJpegDecoder
         self.dataset, self.batch_size, self.prefetch, self.threads = dataset, int(batch_size), int(prefetch), int(threads)
         self.device = None if device is None else torch.device(device)
         self.size = tuple(size) if size is not None else dataset.size
-        self.dec = DeviceJpegDecoder(device=self.device if self.device is not None else 'cpu', threads=self.threads)
+        self.dec = DeviceJpegDecoder(device=self.device if self.device is not None else 'cpu', threads=self.threads, entropy=entropy,
+                                     subseq_bits=subseq_bits)
         self.pipe = None
         # pinned coefficient slots: [buffer | None, event of its last upload | None]; one per batch in flight + the one in use
         self._slots, self._turn = [[None, None] for _ in range(self.prefetch + 2)], 0

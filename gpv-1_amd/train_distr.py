@@ -240,7 +240,8 @@ def file_datasets(cfg, batch_size, device, train=True, evals=True):
     mix per name as train_distr.py:163-166 / :328-341 build it).  A missing sample file or image directory raises, naming the path."""
     from .datasets import DATASETS, CocoMultitaskDataset, DeviceLoader
     tr_cfg = cfg.training
-    kw = dict(device=device, threads=max(1, min(16, int(tr_cfg.get('num_workers', 8)))), prefetch=int(tr_cfg.get('prefetch', 1)))
+    kw = dict(device=device, threads=max(1, min(16, int(tr_cfg.get('num_workers', 8)))), prefetch=int(tr_cfg.get('prefetch', 1)),
+              entropy=os.environ.get('GPV_JPEG_ENTROPY') or tr_cfg.get('jpeg_entropy', 'host'))    # 'device': Huffman walk on the GPU (opt-in)
     if 'task_configs' not in cfg:
         raise KeyError('training.data_source: files needs a task_configs tree (gpv1_amd.default_config)')
     train_ds, eval_ds = None, None
