@@ -915,7 +915,7 @@ __global__ __launch_bounds__(256) void s2_dgrad_fill_kernel(bf16* __restrict__ d
 
 }  // namespace
 
-extern "C" int gpv_abi_version(void) { return 1; }
+extern "C" int gpv_abi_version(void) { return 2; }
 
 extern "C" int gpv_gemm(const gpv_gemm_args* a, void* stream) {
   if (!a || !a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch <= 0) return (int)hipErrorInvalidValue;

@@ -10,6 +10,9 @@ import threading
 
 import torch
 
+from . import _native
+
+ABI_VERSION = 2        # gpv_abi_version() of the library this mirror was written against: the layout of every struct below
 BF16, F32 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 KMAJOR, TRANS = 0, 1
@@ -18,8 +21,8 @@ _LIB = None
 # GPV_TUNING_LIB=1 (tools/ only): the -DGPV_TUNING build of the same sources -- environment knobs of the launch heuristics, timing ablations,
 # experimental kernels (`make -C gpv-1_amd/csrc tuning`).  The production library reads no environment.
 TUNING = os.environ.get('GPV_TUNING_LIB', '0') == '1'
-_LIB_PATH = os.environ.get('GPV_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc',
-                                                          'libgpv_hip_tuning.so' if TUNING else 'libgpv_hip.so')
+_LIB_PATH = os.environ.get('GPV_HIP_LIB') or (os.path.join(os.path.dirname(_native.lib_path('hip')), 'libgpv_hip_tuning.so') if TUNING
+                                               else _native.lib_path('hip'))
 
 
 class GemmArgs(C.Structure):
@@ -94,15 +97,13 @@ class ImageDesc(C.Structure):
 def lib():
     global _LIB
     if _LIB is None:
-        if not os.path.exists(_LIB_PATH):
-            raise RuntimeError(
-                f'gpv1_amd: HIP kernel library not found at {_LIB_PATH}. Build it with '
-                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
-                f'There is no CPU/eager fallback by design.')
-        _LIB = C.CDLL(_LIB_PATH)
-        _LIB.gpv_abi_version.restype = C.c_int
-        if _LIB.gpv_abi_version() != 1:
-            raise RuntimeError('gpv1_amd: libgpv_hip.so ABI version mismatch')
+        # only the version query gets argtypes: the hot-path entry points are called 1500 times per step and keep ctypes' default
+        # argument conversion
+        handle = _native.load('hip', {'gpv_abi_version': []}, _LIB_PATH)
+        if handle.gpv_abi_version() != ABI_VERSION:
+            raise RuntimeError(f'gpv1_amd: libgpv_hip.so ABI version mismatch: the library reports {handle.gpv_abi_version()}, '
+                               f'this mirror needs {ABI_VERSION}')
+        _LIB = handle
     return _LIB
 
 

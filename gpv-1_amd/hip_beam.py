@@ -1,14 +1,14 @@
 """ctypes binding of libgpv_beam.so (C ABI in include/gpv_beam.h): the beam search step and the KV-cache reorder on the device.
 
-A sixth library next to libgpv_hip.so (``hip.EXPORTS``), libgpv_eval.so, libgpv_cap.so, libgpv_match.so and libgpv_health.so: those
-export lists are pinned.  Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.  Nothing
-here synchronises or allocates: both calls are capturable.  The rule is stated in ``gpv1_amd.beam``.
+Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.  Nothing here synchronises or
+allocates: both calls are capturable.  The rule is stated in ``gpv1_amd.beam``.
 """
 import ctypes as C
-import os
+from functools import partial
 
 import torch
 
+from . import _native
 from . import beam as rule
 from .hip import _chk, _stream
 
@@ -16,7 +16,8 @@ EXPORTS = ['gpv_beam_reorder', 'gpv_beam_step']
 MAX_K, MAX_T, MAX_LAYERS = rule.MAX_K, rule.MAX_T, 8      # GPV_BEAM_MAX_K, GPV_BEAM_MAX_T, GPV_BEAM_MAX_LAYERS
 _DTYPES = {torch.bfloat16: 0, torch.float32: 1}           # GPV_BEAM_BF16, GPV_BEAM_F32
 _LIB = None
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libgpv_beam.so')
+_LIB_PATH = _native.lib_path('beam')
+_want = partial(_native.want, 'hip_beam')
 
 
 class BeamArgs(C.Structure):
@@ -31,28 +32,14 @@ class ReorderArgs(C.Structure):
                 ('T', C.c_int), ('D', C.c_int), ('upto', C.c_int), ('dtype', C.c_int)]
 
 
+_SIGNATURES = {'gpv_beam_step': [C.POINTER(BeamArgs), C.c_void_p], 'gpv_beam_reorder': [C.POINTER(ReorderArgs), C.c_void_p]}
+
+
 def lib():
     global _LIB
     if _LIB is None:
-        if not os.path.exists(_LIB_PATH):
-            raise RuntimeError(
-                f'gpv1_amd: beam search kernel library not found at {_LIB_PATH}. Build it with '
-                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
-                f'There is no CPU/eager fallback by design.')
-        _LIB = C.CDLL(_LIB_PATH)
-        _LIB.gpv_beam_step.restype = C.c_int
-        _LIB.gpv_beam_step.argtypes = [C.POINTER(BeamArgs), C.c_void_p]
-        _LIB.gpv_beam_reorder.restype = C.c_int
-        _LIB.gpv_beam_reorder.argtypes = [C.POINTER(ReorderArgs), C.c_void_p]
+        _LIB = _native.load('beam', _SIGNATURES, _LIB_PATH)
     return _LIB
-
-
-def _want(name, t, dtype, shape):
-    if not t.is_cuda:
-        raise RuntimeError(f'gpv1_amd: hip_beam: {name} must live on the GPU (no CPU fallback exists for the device beam step)')
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f'hip_beam: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
-    return t.data_ptr()
 
 
 def step(logits, lse, seq_lp, seqs, tok, parent, finished, length, t, mode, pad_id, stop_id, inv_pen=None, vocab_mask=None):

@@ -1,13 +1,13 @@
 """ctypes binding of libgpv_cap.so (C ABI in include/gpv_cap.h): device-side Bleu / CIDEr-D caption scoring.
 
-A third library next to libgpv_hip.so (the hot path, ``hip.EXPORTS``) and libgpv_eval.so (detection AP, ``hip_eval.EXPORTS``): both
-export lists are pinned.  Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.
+Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.
 """
 import ctypes as C
-import os
+from functools import partial
 
 import torch
 
+from . import _native
 from .hip import _chk, _p, _stream
 
 EXPORTS = ['gpv_cap_scores']
@@ -19,28 +19,17 @@ ERR_BITS = {1: 'the n-gram table is full (capacity too small for the references)
             2: f'a word id inside a caption is outside 1..{MAX_WORD}',
             4: 'a reference n-gram was not found in the table'}
 _LIB = None
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libgpv_cap.so')
+_LIB_PATH = _native.lib_path('cap')
+_SIGNATURES = {'gpv_cap_scores': ([C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 + [C.c_longlong] +
+                                  [C.c_void_p] * 8)}
+_want = partial(_native.want, 'caption_scores')
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        if not os.path.exists(_LIB_PATH):
-            raise RuntimeError(
-                f'gpv1_amd: caption scoring kernel library not found at {_LIB_PATH}. Build it with '
-                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
-                f'There is no CPU/eager fallback by design.')
-        _LIB = C.CDLL(_LIB_PATH)
-        _LIB.gpv_cap_scores.restype = C.c_int
-        _LIB.gpv_cap_scores.argtypes = ([C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 + [C.c_longlong] +
-                                        [C.c_void_p] * 8)
+        _LIB = _native.load('cap', _SIGNATURES, _LIB_PATH)
     return _LIB
-
-
-def _want(name, t, dtype, shape):
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f'caption_scores: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
-    return _p(t)
 
 
 def table_capacity(occurrences):

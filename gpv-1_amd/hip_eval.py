@@ -1,40 +1,29 @@
 """ctypes binding of libgpv_eval.so (C ABI in include/gpv_eval.h): device-side scoring for train-time evaluation.
 
-A library of its own next to libgpv_hip.so: that one is the reference's hot path and its 52 entry points are pinned
-(``hip.EXPORTS``); evaluation is outside that boundary.  Same rules as ``hip``: no CPU / eager fallback -- a missing library or a
-CPU tensor is an error.
+Evaluation is outside the hot-path boundary of libgpv_hip.so, whose entry points are pinned (``hip.EXPORTS``).  Same rules as
+``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.
 """
 import ctypes as C
-import os
+from functools import partial
 
 import torch
 
-from .hip import _chk, _p, _stream
+from . import _native
+from .hip import _chk, _stream
 
 EXPORTS = ['gpv_eval_det_ap']
 MAX_Q = 1024
 _LIB = None
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libgpv_eval.so')
+_LIB_PATH = _native.lib_path('eval')
+_SIGNATURES = {'gpv_eval_det_ap': [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 5}
+_want = partial(_native.want, 'det_ap')
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        if not os.path.exists(_LIB_PATH):
-            raise RuntimeError(
-                f'gpv1_amd: evaluation kernel library not found at {_LIB_PATH}. Build it with '
-                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
-                f'There is no CPU/eager fallback by design.')
-        _LIB = C.CDLL(_LIB_PATH)
-        _LIB.gpv_eval_det_ap.restype = C.c_int
-        _LIB.gpv_eval_det_ap.argtypes = [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 5
+        _LIB = _native.load('eval', _SIGNATURES, _LIB_PATH)
     return _LIB
-
-
-def _want(name, t, dtype, shape):
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f'det_ap: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
-    return _p(t)
 
 
 def det_ap(rel_logits, boxes, gt, gt_count, iou_thresh=0.5, score=None, order=None, tp=None, ap=None):

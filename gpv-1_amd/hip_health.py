@@ -1,17 +1,16 @@
 """ctypes binding of libgpv_health.so (C ABI in include/gpv_health.h): per-segment tensor statistics, their device ring and the
 first-non-finite latch -- the kernels of the training flight recorder (``gpv1_amd.health``).
 
-A fifth library next to libgpv_hip.so (``hip.EXPORTS``), libgpv_eval.so, libgpv_cap.so and libgpv_match.so: those export lists are
-pinned.  Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.  Nothing here synchronises,
+Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.  Nothing here synchronises,
 allocates or reads back; every call can be captured in a graph.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
-from .hip import _chk, _p, _stream
+from . import _native
+from .hip import _chk, _stream
 
 EXPORTS = ['gpv_health_commit', 'gpv_health_stats']
 BLOCK = 16384          # GPV_HEALTH_BLOCK: elements per block of the pinned summation order
@@ -26,31 +25,20 @@ SEG = np.dtype([('ptr', '<u8'), ('n', '<i8'), ('dtype', '<i4'), ('pad', '<i4'), 
 WORK = np.dtype([('seg', '<i4'), ('block', '<i4')])
 assert ROW.itemsize == 64 and SEG.itemsize == 32 and WORK.itemsize == 8
 _LIB = None
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libgpv_health.so')
+_LIB_PATH = _native.lib_path('health')
+_SIGNATURES = {'gpv_health_stats': [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+               'gpv_health_commit': [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]}
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        if not os.path.exists(_LIB_PATH):
-            raise RuntimeError(
-                f'gpv1_amd: flight-recorder kernel library not found at {_LIB_PATH}. Build it with '
-                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
-                f'There is no CPU/eager fallback by design.')
-        _LIB = C.CDLL(_LIB_PATH)
-        _LIB.gpv_health_stats.restype = C.c_int
-        _LIB.gpv_health_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _LIB.gpv_health_commit.restype = C.c_int
-        _LIB.gpv_health_commit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _LIB = _native.load('health', _SIGNATURES, _LIB_PATH)
     return _LIB
 
 
 def _bytes(name, t, nbytes):
-    if not t.is_cuda:
-        raise RuntimeError(f'gpv1_amd: hip_health: {name} must live on the GPU (no CPU fallback exists for the flight recorder)')
-    if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != nbytes or not t.is_contiguous():
-        raise ValueError(f'hip_health: {name} must be a contiguous uint8 tensor of {nbytes} bytes, got {t.dtype} {tuple(t.shape)}')
-    return _p(t)
+    return _native.want('hip_health', name, t, torch.uint8, (nbytes,))
 
 
 def stats(segs, S, work, W, ws, rows):

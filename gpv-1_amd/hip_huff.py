@@ -1,15 +1,13 @@
 """ctypes binding of libgpv_huff.so (C ABI in include/gpv_huff.h): the JPEG Huffman stream decoded on the device.
 
-A seventh library next to libgpv_hip.so (``hip.EXPORTS``), libgpv_eval.so, libgpv_cap.so, libgpv_match.so, libgpv_health.so and
-libgpv_beam.so: those export lists are pinned.  Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor
-is an error.  ``prepare`` is host code (no HIP call, the GIL released); ``decode`` neither synchronises nor allocates.  The rule is
-stated in ``gpv1_amd.jpeg_entropy``.
+Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.  ``prepare`` is host code (no HIP
+call, the GIL released); ``decode`` neither synchronises nor allocates.  The rule is stated in ``gpv1_amd.jpeg_entropy``.
 """
 import ctypes as C
-import os
 
 import torch
 
+from . import _native
 from . import jpeg_entropy as rule
 from .hip import JpegInfo, JpegUnsupported, _chk, _stream
 
@@ -17,7 +15,7 @@ EXPORTS = ['gpv_huff_decode', 'gpv_huff_prepare', 'gpv_huff_workspace_bytes']
 ROUTE_DEVICE, ROUTE_HOST = 0, 1                           # GPV_HUFF_ROUTE_*
 MAX_BITS = rule.MAX_STREAM * 8
 _LIB = None
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libgpv_huff.so')
+_LIB_PATH = _native.lib_path('huff')
 
 
 class HuffTable(C.Structure):
@@ -33,22 +31,16 @@ class HuffDesc(C.Structure):
                 ('blk_h', C.c_ubyte * 8), ('dc', HuffTable * 3), ('ac', HuffTable * 3)]
 
 
+_SIGNATURES = {'gpv_huff_prepare': [C.c_char_p, C.c_int64, C.POINTER(JpegInfo), C.POINTER(HuffDesc), C.c_void_p, C.c_int64,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int)],
+               'gpv_huff_workspace_bytes': [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)],
+               'gpv_huff_decode': [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]}
+
+
 def lib():
     global _LIB
     if _LIB is None:
-        if not os.path.exists(_LIB_PATH):
-            raise RuntimeError(
-                f'gpv1_amd: JPEG entropy kernel library not found at {_LIB_PATH}. Build it with '
-                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
-                f'There is no CPU/eager fallback by design.')
-        _LIB = C.CDLL(_LIB_PATH)
-        _LIB.gpv_huff_prepare.restype = C.c_int
-        _LIB.gpv_huff_prepare.argtypes = [C.c_char_p, C.c_int64, C.POINTER(JpegInfo), C.POINTER(HuffDesc), C.c_void_p, C.c_int64,
-                                          C.POINTER(C.c_int64), C.POINTER(C.c_int)]
-        _LIB.gpv_huff_workspace_bytes.restype = C.c_int
-        _LIB.gpv_huff_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)]
-        _LIB.gpv_huff_decode.restype = C.c_int
-        _LIB.gpv_huff_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        _LIB = _native.load('huff', _SIGNATURES, _LIB_PATH)
     return _LIB
 
 
@@ -87,10 +79,7 @@ def decode(descs_dev, B, subseq_bits, max_nbits, workspace):
     """gpv_huff_decode on the current stream: one launch, no sync.  descs_dev = uint8 device tensor holding B packed HuffDesc structs
     (their stream / coefs / status pointers set), workspace = uint8 device tensor of at least workspace_bytes(...) bytes."""
     for name, t in (('descs', descs_dev), ('workspace', workspace)):
-        if not t.is_cuda:
-            raise RuntimeError(f'gpv1_amd: hip_huff: {name} must live on the GPU (no CPU fallback exists for the device entropy decoder)')
-        if t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError(f'hip_huff.decode: {name} must be a contiguous uint8 tensor, got {t.dtype}')
+        _native.want('hip_huff.decode', name, t, torch.uint8, t.shape)          # any shape: the sizes are checked in bytes below
     need = workspace_bytes(B, subseq_bits, max_nbits)
     if descs_dev.numel() < B * C.sizeof(HuffDesc):
         raise ValueError(f'hip_huff.decode: descs holds {descs_dev.numel()} bytes, {B * C.sizeof(HuffDesc)} needed for {B} descriptors')

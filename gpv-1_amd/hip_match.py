@@ -1,14 +1,14 @@
 """ctypes binding of libgpv_match.so (C ABI in include/gpv_match.h): device-side Hungarian matching and set criterion for box batches.
 
-A fourth library next to libgpv_hip.so (``hip.EXPORTS``), libgpv_eval.so (``hip_eval.EXPORTS``) and libgpv_cap.so
-(``hip_cap.EXPORTS``): those export lists are pinned.  Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU
-tensor is an error.  Nothing here synchronises: the caller reads ``status`` after its own device-to-host copy (``check_status``).
+Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.  Nothing here synchronises: the
+caller reads ``status`` after its own device-to-host copy (``check_status``).
 """
 import ctypes as C
-import os
+from functools import partial
 
 import torch
 
+from . import _native
 from .hip import _chk, _p, _stream
 
 EXPORTS = ['gpv_match_boxes', 'gpv_match_lsap', 'gpv_match_set_loss']
@@ -19,33 +19,18 @@ ERR_BITS = {1: 'the matching cost has a NaN or -inf entry (or a label outside th
             2: 'the matching cost is infeasible (a search found only +inf)',
             4: 'a predicted or target box is degenerate (x1 < x0 or y1 < y0)'}
 _LIB = None
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libgpv_match.so')
+_LIB_PATH = _native.lib_path('match')
+_SIGNATURES = {'gpv_match_lsap': [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 5,
+               'gpv_match_boxes': [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_float] * 3 + [C.c_void_p] * 6,
+               'gpv_match_set_loss': [C.c_void_p] * 8 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 7}
+_want = partial(_native.want, 'hip_match')
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        if not os.path.exists(_LIB_PATH):
-            raise RuntimeError(
-                f'gpv1_amd: matching kernel library not found at {_LIB_PATH}. Build it with '
-                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
-                f'There is no CPU/eager fallback by design.')
-        _LIB = C.CDLL(_LIB_PATH)
-        _LIB.gpv_match_lsap.restype = C.c_int
-        _LIB.gpv_match_lsap.argtypes = [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 5
-        _LIB.gpv_match_boxes.restype = C.c_int
-        _LIB.gpv_match_boxes.argtypes = [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_float] * 3 + [C.c_void_p] * 6
-        _LIB.gpv_match_set_loss.restype = C.c_int
-        _LIB.gpv_match_set_loss.argtypes = [C.c_void_p] * 8 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 7
+        _LIB = _native.load('match', _SIGNATURES, _LIB_PATH)
     return _LIB
-
-
-def _want(name, t, dtype, shape):
-    if not t.is_cuda:
-        raise RuntimeError(f'gpv1_amd: hip_match: {name} must live on the GPU (no CPU fallback exists for the device matcher)')
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f'hip_match: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
-    return _p(t)
 
 
 def supported(Q, Gmax):

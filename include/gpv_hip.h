@@ -35,7 +35,7 @@ extern "C" {
 #define GPV_KMAJOR 0 /* element (row r, red k) at ptr[r*ld + k]  (nn.Linear weight, activations) */
 #define GPV_TRANS 1  /* element (row r, red k) at ptr[k*ld + r]  (reduction index is the slow dim) */
 
-int gpv_abi_version(void); /* = 1 */
+int gpv_abi_version(void); /* = 2: raised whenever a struct below changes its layout; a loader refuses any other number */
 /* writes the NUL-terminated build id (sha256 prefix of the sources the library was compiled from: csrc/Makefile BUILD_ID) into the
  * HOST buffer `buf` of `cap` bytes; 0 = ok.  No reference counterpart: it lets a loader refuse a library that is older than the
  * tree next to it (__graft_entry__.build()). */

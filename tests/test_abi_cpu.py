@@ -1,45 +1,97 @@
-"""C-ABI checks that need no GPU: the shared library loads, exports exactly the entry points include/gpv_hip.h declares,
-and the ctypes mirrors in gpv-1_amd/hip.py have the C layout (sizes and field offsets, via a gcc-compiled probe)."""
+"""C-ABI checks that need no GPU, for every native library of gpv1_amd._native.LIBRARIES: it loads, exports exactly the entry points
+its public header declares and its binding module lists, the ctypes mirrors have the C layout (sizes and field offsets, via a
+gcc-compiled probe), the argtypes are the header's prototypes and the constants of gpv-1_amd/hip.py are the header's.
+
+A new library adds rows to PINNED, SIGNATURES and (if it has structs) STRUCTS below; the test bodies stay as they are."""
 import ctypes
 import os
 import re
 import subprocess
 import sys
 
+import pytest
+
+from tests import abi_probe as probe
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'gpv_hip.h')
-
-
-def declared():
-    src = open(HEADER).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    src = re.sub(r'#ifdef GPV_TUNING.*?#endif', '', src, flags=re.S)       # tuning-build-only entry points are not the production ABI
-    return sorted(set(re.findall(r'\bint\s+(gpv_\w+)\s*\(', src)))
+# the pinned export lists (the hot path's by its count: hip.EXPORTS spells the names)
+PINNED = {'hip': 52,
+          'eval': ['gpv_eval_det_ap'],
+          'cap': ['gpv_cap_scores'],
+          'match': ['gpv_match_boxes', 'gpv_match_lsap', 'gpv_match_set_loss'],
+          'health': ['gpv_health_commit', 'gpv_health_stats'],
+          'beam': ['gpv_beam_reorder', 'gpv_beam_step'],
+          'huff': ['gpv_huff_decode', 'gpv_huff_prepare', 'gpv_huff_workspace_bytes']}
+NO_GETENV = ('hip', 'huff')          # libraries that must not read the environment
+# C struct -> its ctypes mirror in the binding module
+STRUCTS = {'hip': {'gpv_gemm_args': 'GemmArgs', 'gpv_conv_args': 'ConvArgs', 'gpv_attn_args': 'AttnArgs', 'gpv_tt_problem': 'TTProblem',
+                   'gpv_fold_problem': 'FoldProblem', 'gpv_tc_problem': 'TCProblem', 'gpv_image_desc': 'ImageDesc',
+                   'gpv_conv_wgrad_problem': 'ConvWgradProblem', 'gpv_jpeg_info': 'JpegInfo', 'gpv_jpeg_desc': 'JpegDesc'},
+           'beam': {'gpv_beam_args': 'BeamArgs', 'gpv_beam_reorder_args': 'ReorderArgs'},
+           'huff': {'gpv_huff_table': 'HuffTable', 'gpv_huff_desc': 'HuffDesc'}}
+# one letter per parameter: P pointer, i int, f float, q int64_t / long long.  The side libraries only: the hot path's entry points
+# carry no argtypes (hip.lib).
+SIGNATURES = {'gpv_match_set_loss': 'PPPPPPPPiiiiiifPPPPPPP', 'gpv_match_boxes': 'PPPPPiiiiiifffPPPPPP', 'gpv_match_lsap': 'PPiiiiPPPPP',
+              'gpv_eval_det_ap': 'PPPPiiifPPPPP', 'gpv_cap_scores': 'PPPPPiiiiPPiPPqPPPPPPPP', 'gpv_health_stats': 'PiPiPPP',
+              'gpv_health_commit': 'PiiPPPP', 'gpv_huff_prepare': 'PqPPPqPP', 'gpv_huff_workspace_bytes': 'iiqP',
+              'gpv_huff_decode': 'PiiqPqP', 'gpv_beam_step': 'PP', 'gpv_beam_reorder': 'PP'}
+SIDE = [k for k in probe.LIBRARIES if k != 'hip']
 
 
 def lib_path():
-    sys.path.insert(0, ROOT)
-    import gpv1_amd.hip as hip
-    if not os.path.exists(hip._LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return hip._LIB_PATH
+    return probe.built('hip')
 
 
-def test_library_exports_every_declared_entry_point():
-    import gpv1_amd.hip as hip
-    names = declared()
-    assert len(names) == 52, names
-    assert sorted(hip.EXPORTS) == names
-    lib = ctypes.CDLL(lib_path())
+@pytest.mark.parametrize('key', list(probe.LIBRARIES))
+def test_library_exports_exactly_the_declared_entry_points(key):
+    l, mod, names = probe.LIBRARIES[key], probe.module(key), probe.declared(key)
+    assert (len(names) if isinstance(PINNED[key], int) else names) == PINNED[key], names
+    assert sorted(mod.EXPORTS) == names
+    path = probe.built(key)
+    lib = ctypes.CDLL(path)
     for n in names:
-        assert hasattr(lib, n), f'{n} declared in include/gpv_hip.h but not exported'
-    lib.gpv_abi_version.restype = ctypes.c_int
-    assert lib.gpv_abi_version() == 1
+        assert hasattr(lib, n), f'{n} declared in include/{l.header} but not exported'
     # every other exported gpv_* symbol is declared
-    out = subprocess.run(['nm', '-D', '--defined-only', lib_path()], capture_output=True, text=True).stdout
-    exported = sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith('gpv_')})
+    exported = probe.exported(path)
     assert exported == names, set(exported) ^ set(names)
+    # no entry point carries the prefix of another, more specific library: the pinned lists stay apart
+    for other in probe.LIBRARIES.values():
+        if other.key != key and other.prefix.startswith(l.prefix):
+            assert not any(n.startswith(other.prefix) for n in names), other.prefix
+    if key in NO_GETENV:
+        assert not re.search(r'\bgetenv\b', probe.imports(path)), f'{l.file} reads the environment'
+
+
+def test_abi_version_is_one_number():
+    """the library, the mirror's loader and the header's comment carry the same version: an older mirror passes shorter structs"""
+    import gpv1_amd.hip as hip
+    lib = ctypes.CDLL(lib_path())
+    lib.gpv_abi_version.restype = ctypes.c_int
+    assert lib.gpv_abi_version() == hip.ABI_VERSION == 2
+    assert re.search(r'int gpv_abi_version\(void\); /\* = (\d+)\b', open(HEADER).read()).group(1) == str(hip.ABI_VERSION)
+
+
+@pytest.mark.parametrize('key', SIDE)
+def test_argtypes_are_the_header_prototypes(key):
+    """class by class, position by position: a hand-counted run of argtypes that is one short shifts every later argument"""
+    mod, protos = probe.module(key), probe.prototypes(key)
+    assert sorted(protos) == sorted(mod.EXPORTS)
+    probe.built(key)
+    for name, sig in protos.items():
+        assert sig == SIGNATURES[name], name
+        fn = getattr(mod.lib(), name)
+        assert fn.restype is ctypes.c_int and probe.argtypes_classes(fn) == sig, name
+
+
+def test_header_constants_are_the_mirrors():
+    """every #define GPV_<NAME> <int> of include/gpv_hip.h that gpv1_amd.hip repeats as <NAME> has the header's value"""
+    import gpv1_amd.hip as hip
+    consts = {k: int(v) for k, v in re.findall(r'#define\s+GPV_(\w+)\s+(\d+)\b', probe.source('hip'))}
+    found = {k: v for k, v in consts.items() if type(getattr(hip, k, None)) is int}
+    assert {k: getattr(hip, k) for k in found} == found
+    assert sum(k.startswith('OPT_') for k in consts) == sum(k.startswith('OPT_') for k in found) == 21
+    assert {'BF16', 'F32', 'ACT_NONE', 'ACT_RELU', 'ACT_GELU', 'KMAJOR', 'TRANS'} <= set(found)
 
 
 def test_production_library_has_no_tuning_code():
@@ -65,28 +117,19 @@ def test_every_switch_is_documented():
     assert sorted(listed) == sorted(names), (sorted(set(names) - listed), sorted(listed - set(names)))
 
 
-def test_ctypes_structs_match_the_c_layout(tmp_path):
-    import gpv1_amd.hip as hip
-    pairs = (('gpv_gemm_args', hip.GemmArgs), ('gpv_conv_args', hip.ConvArgs), ('gpv_attn_args', hip.AttnArgs), ('gpv_tt_problem', hip.TTProblem), ('gpv_fold_problem', hip.FoldProblem), ('gpv_tc_problem', hip.TCProblem), ('gpv_image_desc', hip.ImageDesc),
-             ('gpv_conv_wgrad_problem', hip.ConvWgradProblem), ('gpv_jpeg_info', hip.JpegInfo), ('gpv_jpeg_desc', hip.JpegDesc))
-    prog = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
+@pytest.mark.parametrize('key', list(STRUCTS))
+def test_ctypes_structs_match_the_c_layout(key, tmp_path):
+    pairs = [(cname, getattr(probe.module(key), mirror)) for cname, mirror in STRUCTS[key].items()]
+    layout = probe.c_layout(tmp_path, [probe.header_path(key)], pairs)
     for cname, cls in pairs:
-        prog.append(f'  printf("{cname} %zu", sizeof({cname}));')
-        for f, _ in cls._fields_:
-            prog.append(f'  printf(" %zu", offsetof({cname}, {f}));')
-        prog.append('  printf("\\n");')
-    prog += ['  return 0;', '}']
-    c = tmp_path / 'probe.c'
-    c.write_text('\n'.join(prog))
-    exe = tmp_path / 'probe'
-    subprocess.run(['gcc', '-std=c99', '-o', str(exe), str(c)], check=True)
-    lines = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.strip().splitlines()
-    for (cname, cls), line in zip(pairs, lines):
-        vals = line.split()
-        assert vals[0] == cname
-        assert int(vals[1]) == ctypes.sizeof(cls), (cname, vals[1], ctypes.sizeof(cls))
-        offs = [int(v) for v in vals[2:]]
-        assert offs == [getattr(cls, f).offset for f, _ in cls._fields_], cname
+        assert layout[cname] == probe.ctypes_layout(cls), (cname, layout[cname], probe.ctypes_layout(cls))
+
+
+@pytest.mark.parametrize('key', list(probe.LIBRARIES))
+def test_every_ctypes_mirror_is_probed(key):
+    mod = probe.module(key)
+    mirrors = {n for n, v in vars(mod).items() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v.__module__ == mod.__name__}
+    assert mirrors == set(STRUCTS.get(key, {}).values())
 
 
 def test_product_refuses_to_run_without_the_library(monkeypatch, tmp_path):

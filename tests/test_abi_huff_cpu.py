@@ -1,6 +1,5 @@
-"""C-ABI checks of libgpv_huff.so that need no GPU: the library exports exactly what include/gpv_huff.h declares and
-gpv1_amd.hip_huff.EXPORTS lists, the ctypes mirrors have the C layout (a gcc-compiled probe, as tests/test_abi_cpu.py does for
-libgpv_hip.so), the header's constants are the rule module's, and bad extents are refused before any launch."""
+"""C-ABI checks of libgpv_huff.so that need no GPU: the Makefile builds it with the other six, the header's
+constants are the rule module's, and bad extents are refused before any launch.  (Exports, prototypes and struct layout: tests/test_abi_cpu.py.)"""
 import ctypes
 import os
 import re
@@ -8,63 +7,26 @@ import subprocess
 
 import pytest
 
+from gpv1_amd import _native
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'gpv_huff.h')
 
 
-def declared():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\bint\s+(gpv_\w+)\s*\(', src)))
-
-
 def lib_path():
-    import gpv1_amd.hip_huff as hh
-    if not os.path.exists(hh._LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return hh._LIB_PATH
-
-
-def test_library_exports_exactly_the_declared_entry_points():
-    import gpv1_amd.hip_huff as hh
-    names = declared()
-    assert names == ['gpv_huff_decode', 'gpv_huff_prepare', 'gpv_huff_workspace_bytes'] == sorted(hh.EXPORTS)
-    out = subprocess.run(['nm', '-D', '--defined-only', lib_path()], capture_output=True, text=True, check=True).stdout
-    exported = sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith('gpv_')})
-    assert exported == names
-    und = subprocess.run(['nm', '-D', '--undefined-only', lib_path()], capture_output=True, text=True).stdout
-    assert not re.search(r'\bgetenv\b', und), 'libgpv_huff.so reads the environment'
+    from tests import abi_probe
+    return abi_probe.built('huff')
 
 
 def test_the_seven_libraries_are_listed_by_the_makefile():
-    mk = open(os.path.join(ROOT, 'gpv-1_amd', 'csrc', 'Makefile')).read()
-    all_line = re.search(r'^all:(.*)$', mk, re.M).group(1).split()
-    assert len(all_line) == 7 and 'libgpv_huff.so' in all_line
-    assert re.search(r'^HUFF_SRCS\s*=\s*jpeg_huff\.hip$', mk, re.M) and 'HUFF_HDRS' in mk and 'HUFF_OBJS' in mk
-    assert 'libgpv_huff.so' in re.search(r'^clean:\n\t(.*)$', mk, re.M).group(1)
-
-
-def test_ctypes_structs_match_the_c_layout(tmp_path):
-    import gpv1_amd.hip_huff as hh
-    pairs = (('gpv_huff_table', hh.HuffTable), ('gpv_huff_desc', hh.HuffDesc))
-    prog = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
-    for cname, cls in pairs:
-        prog.append(f'  printf("{cname} %zu", sizeof({cname}));')
-        for f, _ in cls._fields_:
-            prog.append(f'  printf(" %zu", offsetof({cname}, {f}));')
-        prog.append('  printf("\\n");')
-    prog += ['  return 0;', '}']
-    c = tmp_path / 'probe.c'
-    c.write_text('\n'.join(prog))
-    exe = tmp_path / 'probe'
-    subprocess.run(['gcc', '-std=c99', '-o', str(exe), str(c)], check=True)
-    lines = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.strip().splitlines()
-    for (cname, cls), line in zip(pairs, lines):
-        vals = line.split()
-        assert vals[0] == cname
-        assert int(vals[1]) == ctypes.sizeof(cls), (cname, vals[1], ctypes.sizeof(cls))
-        assert [int(v) for v in vals[2:]] == [getattr(cls, f).offset for f, _ in cls._fields_], cname
-    assert ctypes.sizeof(hh.HuffDesc) % 8 == 0                                    # the kernel copies it to LDS in 8-byte words
+    """what the Makefile builds, not what it says: a dry run links seven libraries, this one from jpeg_huff.o, and clean names them all"""
+    csrc = os.path.join(ROOT, 'gpv-1_amd', 'csrc')
+    dry = subprocess.run(['make', '-n', '-B', '-C', csrc, 'all'], capture_output=True, text=True, check=True).stdout.splitlines()
+    links = {l.split()[-1]: l.split() for l in dry if ' -shared ' in l}
+    assert sorted(links) == sorted(l.file for l in _native.LIBRARIES.values()) and len(links) == 7
+    assert 'jpeg_huff.o' in links['libgpv_huff.so']
+    clean = subprocess.run(['make', '-n', '-C', csrc, 'clean'], capture_output=True, text=True, check=True).stdout.split()
+    assert set(links) <= set(clean)
 
 
 def test_header_constants_are_the_rule_modules():
@@ -77,6 +39,7 @@ def test_header_constants_are_the_rule_modules():
     assert (const['GPV_HUFF_ROUTE_DEVICE'], const['GPV_HUFF_ROUTE_HOST']) == (hh.ROUTE_DEVICE, hh.ROUTE_HOST)
     # the workspace holds two states (8 bytes), two counts, two change words and one first-block word per subsequence
     assert const['GPV_HUFF_WS_PER_SUB'] >= 2 * 8 + 5 * 4 and const['GPV_HUFF_WS_PER_SUB'] % 16 == 0
+    assert ctypes.sizeof(hh.HuffDesc) % 8 == 0                                    # the kernel copies it to LDS in 8-byte words
 
 
 def test_bad_extents_are_refused_before_a_launch():

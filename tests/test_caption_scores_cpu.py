@@ -207,21 +207,10 @@ def test_caption_scorer_host_through_the_metric_loop_and_the_driver(shim, tmp_pa
 
 
 def test_cap_library_exports_exactly_the_declared_entry_points():
-    import gpv1_amd.hip as hip
-    import gpv1_amd.hip_eval as hip_eval
+    """exports, header and nm: tests/test_abi_cpu.py, for every library; here what is the caption library's own"""
     import gpv1_amd.hip_cap as hip_cap
-    if not os.path.exists(hip_cap._LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    header = os.path.join(ROOT, 'include', 'gpv_cap.h')
-    src = re.sub(r'/\*.*?\*/', '', open(header).read(), flags=re.S)
-    declared = sorted(set(re.findall(r'\bint\s+(gpv_cap_\w+)\s*\(', src)))
-    assert declared == sorted(hip_cap.EXPORTS) == ['gpv_cap_scores']
-    out = subprocess.run(['nm', '-D', '--defined-only', hip_cap._LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith('gpv_')})
-    assert exported == declared
-    # the two pinned ABIs are untouched
-    assert len(hip.EXPORTS) == 52 and not any(n.startswith('gpv_cap_') for n in hip.EXPORTS) and hip_eval.EXPORTS == ['gpv_eval_det_ap']
+    from tests import abi_probe
+    header, src = abi_probe.header_path('cap'), abi_probe.source('cap')
     # plain C: the header compiles as C99 on its own, and the mirror's limits are the header's
     subprocess.run(['gcc', '-std=c99', '-fsyntax-only', '-x', 'c', header], check=True)
     limits = dict(re.findall(r'#define\s+(GPV_CAP_\w+)\s+(\d+)', src))

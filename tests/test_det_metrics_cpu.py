@@ -5,7 +5,6 @@ training driver."""
 import json
 import os
 import random
-import re
 import subprocess
 
 import numpy as np
@@ -172,18 +171,8 @@ def test_detection_evaluator_classes(task, tmp_path):
 
 
 def test_eval_library_exports_exactly_the_declared_entry_points():
-    import gpv1_amd.hip as hip
+    """exports, header and nm: tests/test_abi_cpu.py, for every library; here what is the evaluation library's own"""
     import gpv1_amd.hip_eval as hip_eval
-    if not os.path.exists(hip_eval._LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'gpv_eval.h')).read(), flags=re.S)
-    declared = sorted(set(re.findall(r'\bint\s+(gpv_eval_\w+)\s*\(', src)))
-    assert declared == sorted(hip_eval.EXPORTS) == ['gpv_eval_det_ap']
-    out = subprocess.run(['nm', '-D', '--defined-only', hip_eval._LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith('gpv_')})
-    assert exported == declared
-    assert len(hip.EXPORTS) == 52 and not any(n.startswith('gpv_eval_') for n in hip.EXPORTS)      # the hot-path ABI is untouched
     # plain C: the header compiles as C99 on its own
     subprocess.run(['gcc', '-std=c99', '-fsyntax-only', '-x', 'c', os.path.join(ROOT, 'include', 'gpv_eval.h')], check=True)
     # no CPU path: the mirror refuses host tensors before anything is launched

@@ -158,23 +158,10 @@ def test_mirror_refuses_cpu_tensors_and_shapes_outside_the_limits():
 
 
 def test_match_library_exports_exactly_the_declared_entry_points():
-    import gpv1_amd.hip as hip
-    import gpv1_amd.hip_cap as hip_cap
-    import gpv1_amd.hip_eval as hip_eval
+    """exports, header and nm: tests/test_abi_cpu.py, for every library; here what is the matching library's own"""
     import gpv1_amd.hip_match as hip_match
-    if not os.path.exists(hip_match._LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    header = os.path.join(ROOT, 'include', 'gpv_match.h')
-    src = re.sub(r'/\*.*?\*/', '', open(header).read(), flags=re.S)
-    declared = sorted(set(re.findall(r'\bint\s+(gpv_match_\w+)\s*\(', src)))
-    assert declared == sorted(hip_match.EXPORTS) == ['gpv_match_boxes', 'gpv_match_lsap', 'gpv_match_set_loss']
-    out = subprocess.run(['nm', '-D', '--defined-only', hip_match._LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith('gpv_')})
-    assert exported == declared
-    # the three pinned ABIs are untouched
-    assert len(hip.EXPORTS) == 52 and hip_eval.EXPORTS == ['gpv_eval_det_ap'] and hip_cap.EXPORTS == ['gpv_cap_scores']
-    assert not any(n.startswith('gpv_match_') for n in hip.EXPORTS)
+    from tests import abi_probe
+    header, src = abi_probe.header_path('match'), abi_probe.source('match')
     # plain C: the header compiles as C99 on its own, and the mirror's limits are the header's
     subprocess.run(['gcc', '-std=c99', '-fsyntax-only', '-x', 'c', header], check=True)
     limits = dict(re.findall(r'#define\s+(GPV_MATCH_\w+)\s+(\d+)', src))
