@@ -21,6 +21,15 @@ LIBRARIES = {l.key: l for l in (
     Library('beam', 'libgpv_beam.so', 'gpv_beam.h', 'gpv_beam_', 'beam search'),
     Library('huff', 'libgpv_huff.so', 'gpv_huff.h', 'gpv_huff_', 'JPEG entropy'),
 )}
+# Libraries beside the seven (the Makefile's `extensions` target): the same rules, build checks and loader; a table of their own
+# because the number of LIBRARIES is pinned by the ABI tests.
+EXTENSIONS = {l.key: l for l in (
+    Library('enc', 'libgpv_enc.so', 'gpv_enc.h', 'gpv_enc_', 'JPEG encoder'),
+)}
+
+
+def library(key):
+    return LIBRARIES[key] if key in LIBRARIES else EXTENSIONS[key]
 
 
 def module_name(key):
@@ -28,11 +37,11 @@ def module_name(key):
 
 
 def header_path(key):
-    return os.path.join(ROOT, 'include', LIBRARIES[key].header)
+    return os.path.join(ROOT, 'include', library(key).header)
 
 
 def lib_path(key):
-    return os.path.join(ROOT, 'gpv-1_amd', 'csrc', LIBRARIES[key].file)
+    return os.path.join(ROOT, 'gpv-1_amd', 'csrc', library(key).file)
 
 
 def load(key, signatures, path=None):
@@ -41,7 +50,7 @@ def load(key, signatures, path=None):
     path = path or lib_path(key)
     if not os.path.exists(path):
         raise RuntimeError(
-            f'gpv1_amd: {LIBRARIES[key].noun} kernel library not found at {path}. Build it with '
+            f'gpv1_amd: {library(key).noun} kernel library not found at {path}. Build it with '
             f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
             f'There is no CPU/eager fallback by design.')
     lib = C.CDLL(path)

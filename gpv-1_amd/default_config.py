@@ -88,6 +88,7 @@ _TREE = {'exp_name': 'default',
               'data_source': 'synthetic',          # 'files': CocoMultitaskDataset(learning_datasets, task_configs) behind a DeviceLoader
               'prefetch': 1,                       # batches the loader's worker thread prepares ahead (data_source: files)
               'vis_step': 2000,
+              'visualize': 'off',                  # 'device': training visualisations every vis_step steps (gpv1_amd.visualize)
               'log_step': 10,
               'ckpt_step': 2000,
               'lr': 0.0001,

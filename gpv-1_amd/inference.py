@@ -12,6 +12,9 @@ punctuation-attachment rules (a join that glues ``, . ! ? ; : ' n't 's %`` to th
 usage: python -m gpv1_amd.inference [--config some.yaml] ckpt=... inputs.img=img.npy inputs.query="what is this?"
                                       [beam_size=5] [num_output_boxes=5]
                                       [beam.impl=device] [beam.finished=freeze] [beam.length_penalty=0.6]
+                                      [outputs.vis=picture.jpg]
+``outputs.vis`` (the reference's ``inference_util.vis_sample``): the picture the model saw with the ``num_output_boxes`` boxes drawn,
+encoded on the device (gpv1_amd.jpeg_encode.DeviceJpegEncoder) and written to that path.
 """
 import argparse
 import os
@@ -137,12 +140,24 @@ def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=
     return decode_outputs(out, model, num_output_boxes)
 
 
+def write_vis(path, image, boxes, device, colour=(255, 0, 0)):
+    """the picture as preprocess_image hands it to the model, with `boxes` ([n, 4] normalised cx, cy, w, h) outlined -> a JPEG file
+    at `path`, denormalised, drawn and encoded on the device"""
+    from .jpeg_encode import DeviceJpegEncoder
+    from .visualize import stem_layout
+    nested = stem_layout(nested_tensor_from_tensor_list([preprocess_image(image).to(device)]))
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    data = DeviceJpegEncoder(device=device).encode_batch(nested, IMAGENET_MEAN, IMAGENET_STD, boxes=[boxes], colours=[[colour] * len(boxes)])[0]
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--config', default=None, help='YAML file (e.g. the reference configs/exp/gpv.yaml); default: gpv1_amd.default_config')
     ap.add_argument('overrides', nargs='*')
     args = ap.parse_args(argv)
-    # ckpt= inputs.img= inputs.query= beam_size= beam.impl= beam.finished= beam.length_penalty= are added keys
+    # outputs.vis= ckpt= inputs.img= inputs.query= beam_size= beam.impl= beam.finished= beam.length_penalty= are added keys
     cfg = load_config(args.config, args.overrides, strict=False) if args.config else from_dict(default_tree(), args.overrides, strict=False)
     model = GPV(cfg.model).cuda().eval()
     load_model_state(model, cfg.get('ckpt', cfg.eval.ckpt), map_location='cuda:0')
@@ -154,6 +169,11 @@ def main(argv=None):
         print(k)
         print('-' * 80)
         print(v)
+    vis = (cfg.get('outputs', None) or {}).get('vis', None)
+    if vis:
+        write_vis(str(vis), img, pred['boxes'], 'cuda:0')
+        print('-' * 80)
+        print('wrote', vis)
 
 
 if __name__ == '__main__':

@@ -25,7 +25,13 @@ What is reproduced -- everything between the data loader and the checkpoint file
     it is 0 and the log says so (the reference's pycocoevalcap is un-vendored); the reference leaves ``refcocop`` out of the
     sum, so its mAP is logged only.  Evaluation leaves the training state alone: ``model.eval()`` / ``no_grad`` /
     ``model.train()``, no RNG draw, the captured training graphs are replayed afterwards, not recaptured.
-Out of scope: dataset ETL (downloading / preprocessing COCO; READING what it wrote is gpv1_amd.datasets), TensorBoard, HTML.  Without ``eval_datasets`` this driver checkpoints every
+  * training visualisations (``visualize`` :40-133, called at :454-460) with the added key ``training.visualize: device`` (default
+    ``off``: nothing here changes): every ``training.vis_step`` steps (at launch only with ``training.run_vis_at_launch``) rank 0
+    writes ``exp_dir/training_visualizations/<subset>_<step>/`` for ``train`` and ``val`` -- the first
+    ``training.num_vis_samples`` pictures as the model saw them, boxes drawn and JPEG-encoded on the device
+    (gpv1_amd.visualize, csrc/jpeg_enc.hip), and an ``index.html``.  Between steps, outside any graph capture; the batches come from
+    the evaluation datasets (``train`` falls back to the training dataset's first batches when there are none).
+Out of scope: dataset ETL (downloading / preprocessing COCO; READING what it wrote is gpv1_amd.datasets), TensorBoard.  Without ``eval_datasets`` this driver checkpoints every
 ``training.ckpt_step`` steps and at every epoch end into ``model.pth``.
 The dataset is any sequence of ``(image[3,H,W] fp32 normalised, query str | (ids, mask), target dict)``;
 ``SyntheticCocoDataset`` provides BASELINE's synthetic COCO-shaped samples (``training.data_source: synthetic``, the default).
@@ -208,6 +214,21 @@ def evaluate_subset(model, datasets, subset, cfg, epoch, device, log=print, said
     return vqa_acc + cider + det_map + cls_acc
 
 
+def visualize_subsets(model, cfg, step, dataset, eval_datasets, batch_size, device, log=print):
+    """train_distr.py:456-460 on rank 0: `train` and `val` through gpv1_amd.visualize.  A subset's batches are those of its
+    evaluation datasets, one after the other (visualize stops after training.num_vis_samples); without evaluation datasets `train`
+    reads the training dataset from its start (unless a loader feeds it: that loader is in the middle of the epoch) and `val` is left
+    out."""
+    import itertools
+    from .visualize import visualize
+    for subset in ('train', 'val'):
+        sets = list((eval_datasets or {}).get(subset, {}).values()) or ([dataset] if subset == 'train' and getattr(dataset, 'loader', None) is None else [])
+        if not sets:
+            continue
+        log(f'Visualizing {subset} ...')
+        visualize(model, itertools.chain.from_iterable(eval_batches(ds, batch_size, device) for ds in sets), cfg, step, subset)
+
+
 def save_checkpoint(path, model, trainer, epoch, step, metric=0.0):
     """train_distr.py:381-389 (DDP state dict => 'module.' prefix)"""
     sd = {'module.' + k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
@@ -335,8 +356,11 @@ def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
     if rank == 0:
         os.makedirs(cfg.ckpt_dir, exist_ok=True)
     max_steps = cfg.get('max_steps', None)
+    vis_mode = tr_cfg.get('visualize', 'off')
+    if vis_mode not in ('off', 'device'):
+        raise ValueError(f"training.visualize must be 'off' or 'device', got {vis_mode!r}")
     t0 = time.time()
-    launch = True
+    launch = vis_launch = True
     for epoch in range(last_epoch + 1, epochs):
         if eval_datasets is not None and ((not launch) or tr_cfg.get('run_eval_at_launch', True)):
             if rank == 0:
@@ -362,6 +386,12 @@ def train_worker(cfg, dataset=None, device=None, log=print, eval_datasets=None):
             trainer.set_epoch(epoch, it)
             loss = trainer.train_step(imgs, queries, targets)
             step += 1
+            if vis_mode == 'device':
+                # the reference tests the step count before its increment, after the step: the first step of a run visualises only
+                # with run_vis_at_launch
+                if rank == 0 and (step - 1) % tr_cfg.vis_step == 0 and ((not vis_launch) or tr_cfg.run_vis_at_launch):
+                    visualize_subsets(model, cfg, step - 1, dataset, eval_datasets, per_rank, device, log)
+                vis_launch = False
             if rank == 0 and step % tr_cfg.log_step == 0:
                 line = (f'epoch {epoch} step {step} loss {float(loss.detach()) if loss is not None else float("nan"):.4f} '
                         f'lr {trainer.current_lrs()["others"]:.3e} {time.time() - t0:.1f}s')
