@@ -1,5 +1,6 @@
 // libgpv_huff.so: the Huffman stream of baseline JPEG files decoded on the device (include/gpv_huff.h states the rule and the ABI,
-// gpv1_amd.jpeg_entropy is the host statement, jpeg_huff_host.h holds the host pass and the symbol walk).
+// gpv1_amd.jpeg_entropy is the host statement, jpeg_huff_host.h holds the host pass and the symbol walk, jpeg_host.h the header
+// parser and table builder it shares with gpv_jpeg_parse).
 //
 // One workgroup of 1024 threads serves one image, one launch serves the batch:
 //   0. the descriptor (geometry + the six tables, 8.7 KB) is copied to LDS; the coefficients are zeroed with 16-byte stores
@@ -180,8 +181,8 @@ constexpr int64_t kMaxBits = (int64_t)GPV_HUFF_MAX_STREAM * 8;
 
 extern "C" int gpv_huff_prepare(const unsigned char* data, int64_t nbytes, gpv_jpeg_info* info, gpv_huff_desc* desc, unsigned char* out,
                                 int64_t out_capacity, int64_t* stream_cap, int* route) {
-  static thread_local gpv_huff_host::Tables tabs;
-  return gpv_huff_host::prepare(data, nbytes, info, desc, out, out_capacity, stream_cap, route, tabs);
+  static thread_local gpv_huff_host::Frame frame;
+  return gpv_huff_host::prepare(data, nbytes, info, desc, out, out_capacity, stream_cap, route, frame);
 }
 
 extern "C" int gpv_huff_workspace_bytes(int B, int subseq_bits, int64_t max_nbits, int64_t* bytes) {

@@ -15,13 +15,13 @@ gpv_jpeg_parse takes are routed 'host' and keep that parser; what it refuses is 
 import numpy as np
 
 from .hip import JpegInfo, JpegUnsupported
+from .jpeg_encode import ZIGZAG as _ZIGZAG
 
 LOOK = 9
 MIN_S, MAX_S = 64, 4096
 MAX_STREAM = 1 << 27
 ERR_CODE, ERR_SHORT, ERR_EXTENT = 1, 2, 4
-ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-          35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+ZIGZAG = tuple(int(k) for k in _ZIGZAG)                   # plain ints: the walk below indexes with them symbol by symbol
 
 
 def _bad(why):

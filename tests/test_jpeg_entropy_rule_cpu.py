@@ -165,6 +165,63 @@ def test_c_prepare_equals_prepare_host_byte_for_byte(name):
         hip_huff.prepare(read(name), np.zeros(16, np.uint8))                     # a lent buffer that is too small
 
 
+SMALL = [n for n in NAMES if os.path.getsize(os.path.join(GOLD, n + '.jpg')) <= 2100]
+
+
+def _sos_offset(d):
+    """offset of the FF of the SOS marker of a well-formed file (a walk over its segments, not a search for FF DA)"""
+    p = 2
+    while d[p + 1] != 0xDA:
+        p += 2 + ((d[p + 2] << 8) | d[p + 3])
+    return p
+
+
+def _outcome(fn, *args):
+    """(None, result) or (the refusal's class, None): JpegUnsupported against a plain ValueError"""
+    import gpv1_amd.hip as hip
+    try:
+        return None, fn(*args)
+    except ValueError as e:
+        return (hip.JpegUnsupported if isinstance(e, hip.JpegUnsupported) else ValueError), None
+
+
+def test_small_fixture_split():
+    assert len(SMALL) == 12 and set(NAMES) - set(SMALL) == {'c420_big', 'c444_q90'}
+
+
+@pytest.mark.parametrize('name', SMALL)
+def test_the_two_host_entry_points_agree_on_damaged_headers(name):
+    """gpv_jpeg_parse (header pass) and gpv_huff_prepare read the same headers: every cut and every single-byte change of the
+    region up to the SOS marker + 16 gets the same refusal class from both or the same `info` bytes.  Where only prepare refuses
+    (it asks for the Huffman tables at once), the full decode of gpv_jpeg_parse refuses in the same way."""
+    import gpv1_amd.hip as hip
+    from gpv1_amd import hip_huff
+    data = read(name)
+    region = min(len(data), _sos_offset(data) + 16)
+    variants = [data[:cut] for cut in range(region + 1)]
+    for i in range(region):
+        for b in (0x00, 0xFF, (data[i] + 1) & 255):
+            variants.append(data[:i] + bytes([b]) + data[i + 1:])
+    assert len(variants) == 4 * region + 1
+    skipped = accepted = 0
+    for v in variants:
+        e_parse, info = _outcome(hip.jpeg_parse, v)
+        e_prep, prep = _outcome(hip_huff.prepare, v)
+        where = (name, len(v), [i for i in range(min(len(v), region)) if v[i] != data[i]])
+        if e_parse is not None:
+            assert e_prep is e_parse, where                                      # both refuse, in the same way
+        elif e_prep is None:
+            assert bytes(info) == bytes(prep[0]), where                          # both accept
+            accepted += 1
+        elif info.coef_count > 1 << 22:                                          # only prepare refuses: so does the full decode
+            skipped += 1
+        else:
+            e_full, _ = _outcome(hip.jpeg_parse, v, np.zeros(info.coef_count, np.int16))
+            assert e_full is e_prep, where
+    assert skipped <= 0.02 * len(variants), (skipped, len(variants))
+    assert accepted > len(variants) // 4                                         # (most single-byte changes still parse)
+
+
 def test_random_bytes_as_a_stream_end_within_the_pass_bound():
     from gpv1_amd import jpeg_entropy as E
     r = np.random.RandomState(7)

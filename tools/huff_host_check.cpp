@@ -1,11 +1,16 @@
-// Stand-alone check of the host-only half of libgpv_huff.so (gpv-1_amd/csrc/jpeg_huff_host.h) under the host sanitisers: no GPU, no
-// Python.  Build and run from the repository root:
+// Stand-alone check of the host code that reads JPEG files under the host sanitisers: the host-only half of libgpv_huff.so
+// (gpv-1_amd/csrc/jpeg_huff_host.h) and the body of gpv_jpeg_parse with its serial entropy decoder (gpv-1_amd/csrc/jpeg_host.h).  No
+// GPU, no Python.  Build and run from the repository root:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o /tmp/huff_host_check tools/huff_host_check.cpp
 //   /tmp/huff_host_check tests/golden/jpeg/*.jpg
 // Per file: gpv_huff_host::prepare on the file, on every truncation of it (a stride of 7 bytes), on copies with random bytes
 // overwritten, and on random byte strings; then the subsequence iteration of the rule, run sequentially with the very walk the kernel
 // compiles (S = 64, 256, 1024), on the file's stream and on random streams under the file's tables.  The fixed point must equal one
-// walk over the whole stream (coefficients, states and block count) within n_sub passes.  Exit status 0 and "ok" = clean.
+// walk over the whole stream (coefficients, states and block count) within n_sub passes.
+// Every file variant also goes through gpv_jpeg_host::parse: the header pass, then the full decode into an exact-size heap buffer.
+// The two entry points must agree: the same refusal, the same `info`, a missing table refused by the full decode as by prepare; and
+// where prepare routes to the device and the sequential walk reports status 0, its coefficients (DC differences summed per
+// component) must equal the serial decoder's.  Exit status 0 and "ok" = clean.
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -16,6 +21,8 @@ using namespace gpv_huff_host;
 static uint32_t rng_state = 12345;
 static uint32_t rnd() { rng_state = rng_state * 1664525u + 1013904223u; return rng_state >> 8; }
 
+struct State { uint32_t p; int c, z, cnt; };
+
 struct Prepared {
   gpv_jpeg_info info;
   gpv_huff_desc desc;
@@ -23,7 +30,44 @@ struct Prepared {
   int route, err;
 };
 
-static Prepared prep(const std::vector<unsigned char>& f, Tables& tabs) {
+static long serial_decodes = 0, device_compared = 0;
+
+// gpv_jpeg_parse on the same bytes (header pass, then the full decode) against what prepare said
+static void check_parse(const unsigned char* copy, int64_t n, const Prepared& p, Frame& tabs) {
+  gpv_jpeg_info hi;
+  const int he = parse(copy, n, &hi, nullptr, 0, tabs);
+  if (he && p.err != he) { printf("header pass refuses with %d, prepare returns %d\n", he, p.err); exit(2); }
+  if (!p.err && (he || memcmp(&hi, &p.info, sizeof(hi)))) { printf("prepare succeeds, the header pass differs (%d)\n", he); exit(2); }
+  if (he || hi.coef_count > (1 << 22)) return;
+  short* coefs = (short*)malloc(hi.coef_count ? (size_t)hi.coef_count * sizeof(short) : 1);   // exact size: a write past it is a report
+  gpv_jpeg_info fi;
+  const int fe = parse(copy, n, &fi, coefs, hi.coef_count, tabs);
+  ++serial_decodes;
+  if (memcmp(&fi, &hi, sizeof(fi))) { printf("the full decode fills another info than the header pass\n"); exit(2); }
+  if (p.err && fe != p.err) { printf("prepare refuses with %d behind a good header pass, the full decode returns %d\n", p.err, fe); exit(2); }
+  if (!p.err && p.route == GPV_HUFF_ROUTE_DEVICE) {
+    const gpv_huff_desc& d = p.desc;
+    std::vector<short> w((size_t)d.coef_count, 0);
+    State s{0, 0, 0, 0};
+    int status = 0;
+    walk<true>(d, p.stream.data(), d.stream_cap / 4, s.p, s.c, s.z, (uint32_t)d.nbits, d.nbits + 1, s.cnt, w.data(), 0, status);
+    if (s.cnt < d.nblocks) status |= GPV_HUFF_ERR_SHORT;                 // (as the kernel does: the serial decoder reads zero bits on)
+    if (status == 0) {
+      int run[3] = {0, 0, 0};
+      for (int blk = 0; blk < d.nblocks; ++blk) {                        // DC differences -> values, per component in scan order
+        const int c = d.blk_comp[blk % d.blocks_per_mcu];
+        short& dc = w[(size_t)block_address(d, d.blocks_per_mcu, blk)];
+        run[c] += dc;
+        dc = (short)run[c];
+      }
+      if (fe || memcmp(w.data(), coefs, w.size() * sizeof(short))) { printf("the walk and the serial decoder differ (%d)\n", fe); exit(2); }
+      ++device_compared;
+    }
+  }
+  free(coefs);
+}
+
+static Prepared prep(const std::vector<unsigned char>& f, Frame& tabs) {
   Prepared p;
   int64_t cap = 0;
   // an exact-size heap copy: a read past the file is a sanitiser report
@@ -40,11 +84,10 @@ static Prepared prep(const std::vector<unsigned char>& f, Tables& tabs) {
     if (e2 || cap2 != cap || r2 != p.route || memcmp(&i2, &p.info, sizeof(i2)) || memcmp(&d2, &p.desc, sizeof(d2))) { printf("prepare: second call differs\n"); exit(2); }
     if (prepare(copy, (int64_t)f.size(), &i2, &d2, (unsigned char*)p.stream.data(), cap - 1, &cap2, &r2, tabs) != kInvalid) { printf("prepare: short buffer accepted\n"); exit(2); }
   }
+  check_parse(copy, (int64_t)f.size(), p, tabs);
   free(copy);
   return p;
 }
-
-struct State { uint32_t p; int c, z, cnt; };
 
 // the iteration of the rule, sequentially; returns the passes, fills coefs (DC as differences) and the status bits
 static int iterate(const gpv_huff_desc& d, const uint32_t* words, int S, std::vector<short>& coefs, int& status, int& blocks) {
@@ -99,16 +142,19 @@ static void check_stream(const gpv_huff_desc& d, const uint32_t* words, const ch
 }
 
 int main(int argc, char** argv) {
-  static Tables tabs;
-  long prepared = 0, refused = 0, streams = 0;
+  static Frame tabs;
+  long whole_compared = 0, prepared = 0, refused = 0, streams = 0;
   for (int a = 1; a < argc; ++a) {
     FILE* fp = fopen(argv[a], "rb");
     if (!fp) { printf("cannot open %s\n", argv[a]); return 2; }
     std::vector<unsigned char> f;
     for (int ch; (ch = fgetc(fp)) != EOF;) f.push_back((unsigned char)ch);
     fclose(fp);
+    const long before = device_compared;
     Prepared whole = prep(f, tabs);
     if (whole.err) { printf("%s: prepare returned %d\n", argv[a], whole.err); return 2; }
+    if (whole.route == GPV_HUFF_ROUTE_DEVICE && device_compared == before) { printf("%s: the walk reports an error on the whole file\n", argv[a]); return 2; }
+    whole_compared += device_compared - before;
     check_stream(whole.desc, whole.stream.data(), argv[a]);
     ++streams;
     for (size_t cut = 0; cut < f.size(); cut += 7) {                     // truncated copies
@@ -143,6 +189,7 @@ int main(int argc, char** argv) {
     Prepared p = prep(g, tabs);
     p.err ? ++refused : ++prepared;
   }
-  printf("ok: %d files, %ld variants prepared, %ld refused, %ld streams iterated at S = 64, 256, 1024\n", argc - 1, prepared, refused, streams);
+  printf("ok: %d files, %ld variants prepared, %ld refused, %ld streams iterated at S = 64, 256, 1024, %ld serial decodes, %ld device-routed "
+         "variants equal to the serial decoder (%ld of them whole files)\n", argc - 1, prepared, refused, streams, serial_decodes, device_compared, whole_compared);
   return 0;
 }
