@@ -10,25 +10,13 @@ typedef bf16 __attribute__((ext_vector_type(4))) bf16x4;
 typedef bf16 __attribute__((ext_vector_type(2))) bf16x2;
 typedef float __attribute__((ext_vector_type(4))) f32x4;
 
-// Environment knobs of the kernels' launch heuristics (kernel family on / off, blocks per CU, rows per strip, forced tiles, split targets,
-// timing ablations) exist for tools/ only: they are read iff the library was compiled with -DGPV_TUNING (`make tuning` ->
-// libgpv_hip_tuning.so, loaded by gpv1_amd.hip when GPV_TUNING_LIB=1).  The production library (libgpv_hip.so) reads NO environment:
-// every knob is its default, and the run-time switches tests need go through gpv_set_option ("no global state").
-#include <stdlib.h>
-#ifdef GPV_TUNING
-static inline int tune_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#else
-static inline int tune_env(const char*, int dflt) { return dflt; }
-#endif
+#include "host_defs.h"      // tune_env, al16, drop_thresh: what the host-only routing header shares with the kernels
 
 #define GPV_CHECK_LAUNCH() \
   do {                     \
     hipError_t e_ = hipGetLastError(); \
     if (e_ != hipSuccess) return (int)e_; \
   } while (0)
-
-// 16-byte alignment of an operand base: the precondition of every 16-byte vector access and of the LDS-DMA loaders
-__host__ __device__ __forceinline__ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // XCD-aware work order: workgroup b runs on XCD b % 8 (observed dispatch rule, used for speed only).  Give every
 // XCD a CONTIGUOUS range of tiles so that the column tiles of one row panel (same A rows / same conv pixels) share
@@ -146,12 +134,6 @@ __device__ __forceinline__ uint32_t drop_mask(uint64_t seed, uint64_t base, uint
 namespace gpvk { extern const uint64_t* g_seed_dev; }
 __device__ __forceinline__ uint64_t eff_seed(uint64_t seed, const uint64_t* epoch) {
   return epoch ? seed ^ (*epoch * 0x9E3779B97F4A7C15ull) : seed;
-}
-__host__ __device__ __forceinline__ uint32_t drop_thresh(float p) {
-  double t = (double)p * 4294967296.0;
-  if (t < 0) t = 0;
-  if (t > 4294967295.0) t = 4294967295.0;
-  return (uint32_t)t;
 }
 
 // Weights resident in LDS, staged once per workgroup (the streaming kernels): U 16-byte loads of every thread are issued before the

@@ -295,16 +295,9 @@ void c1s_kernel(GemmK p, int ncols) {
   }
 }
 
-// output channels per block: the whole layer when its weights fit the LDS (K <= 128: up to 512 channels), else slices on gridDim.y
-inline int c1s_cols(int K, int N) {
-  const int cap = K <= 128 ? 512 : (K == 256 ? 256 : 128);
-  return N < cap ? N : cap;
-}
-
 template <int K, int NH, bool RES, bool MASK, bool NT, bool LIN = false, int NP = 1, bool BITS = false>
-int c1s_launch_np(const GemmK& k, hipStream_t st) {
-  const int ncols = c1s_cols(k.K, k.N), nsl = k.N / ncols;
-  const size_t lds = (size_t)ncols * K * 2 + (size_t)ncols * sizeof(float);
+int c1s_launch_np(const GemmK& k, const Route& r, hipStream_t st) {
+  const size_t lds = (size_t)r.lds;
   auto fn = c1s_kernel<K, NH, RES, MASK, NT, LIN, NP, BITS>;
   static size_t attr = 0;
   if (lds > 64 * 1024 && lds > attr) {
@@ -312,117 +305,70 @@ int c1s_launch_np(const GemmK& k, hipStream_t st) {
     if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }      // (leave no stale error behind for the next launch check)
     attr = lds;
   }
-  // persistent waves: two blocks of 8 waves per CU when the weights leave room for them, one otherwise
-  const int ntile = (k.M + 15) / 16;
-  static const int bpc = tune_env("GPV_C1S_BLOCKS", 0);
-  int blocks = bpc > 0 ? bpc : (lds <= 72 * 1024 ? 512 : 256);
-  blocks = (blocks + nsl - 1) / nsl;
-  if (blocks * 8 > ntile) blocks = (ntile + 7) / 8;
-  hipLaunchKernelGGL(fn, dim3(blocks, nsl), dim3(512), lds, st, k, ncols);
+  hipLaunchKernelGGL(fn, dim3(r.gx, r.gy), dim3(r.block), lds, st, k, r.ncols);
   GPV_CHECK_LAUNCH();
   return 0;
 }
 
+// the instances that exist (gemm_route.h c1s_select picks only among these; -1 = none, which it never asks for)
 template <int K, int NH, bool RES, bool MASK, bool NT, bool LIN = false, bool BITS = false>
-int c1s_launch(const GemmK& k, hipStream_t st) {
-  const int np = c1s_cols(k.K, k.N) / NH;
-  if (np == 1) return c1s_launch_np<K, NH, RES, MASK, NT, LIN, 1, BITS>(k, st);
-  if constexpr (K <= 128 && NH == 256 && !LIN) { if (np == 2) return c1s_launch_np<K, NH, RES, MASK, NT, LIN, 2, BITS>(k, st); }
+int c1s_launch_p(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.np == 1) return c1s_launch_np<K, NH, RES, MASK, NT, LIN, 1, BITS>(k, r, st);
+  if constexpr (K <= 128 && NH == 256 && !LIN) { if (r.np == 2) return c1s_launch_np<K, NH, RES, MASK, NT, LIN, 2, BITS>(k, r, st); }
   return -1;
 }
 
 template <int K, int NH>
-int c1s_flags(const GemmK& k, hipStream_t st, bool linear) {
-  const bool r = k.res != nullptr, m = k.mask != nullptr, nt = k.nt_io != 0;
-  // gpv_gemm's calls always take the LIN instances (alpha = 1 and no dropout are exact no-ops there): a linear layer's launch is then
-  // told from a convolution's by its NAME -- profiles and bench.py's live HBM-traffic passes (tools/pmc_traffic.py) classify by it
-  if (linear || k.alpha != 1.0f || k.dthresh) {     // linear-layer extras: instantiated for the 256 -> n x 256 shapes only
+int c1s_flags(const GemmK& k, const Route& r, hipStream_t st) {
+  const bool res = r.res, m = r.mask;
+  if (r.lin) {     // linear-layer extras: instantiated for the 256 -> n x 256 shapes only
     if constexpr (K == 256 && NH == 256) {
-      if (nt) return -1;
-      if (r && m) return c1s_launch<K, NH, true, true, false, true>(k, st);
-      if (r) return c1s_launch<K, NH, true, false, false, true>(k, st);
-      if (m) return c1s_launch<K, NH, false, true, false, true>(k, st);
-      return c1s_launch<K, NH, false, false, false, true>(k, st);
+      if (res && m) return c1s_launch_p<K, NH, true, true, false, true>(k, r, st);
+      if (res) return c1s_launch_p<K, NH, true, false, false, true>(k, r, st);
+      if (m) return c1s_launch_p<K, NH, false, true, false, true>(k, r, st);
+      return c1s_launch_p<K, NH, false, false, false, true>(k, r, st);
     } else {
       return -1;
     }
   }
-  if (k.mask_bits || k.out_bits) {
-    // one-bit ReLU masks: the instances the ResNet body uses -- conv3 + residual + ReLU of layer2 / layer3 writes them (K = 128 | 256,
-    // 256 channels per pass), conv1's backward-data (residual + mask) of layer2 / layer3 / layer4.0 reads them (+ K = 512 -> 128-wide passes)
-    if (nt || !r || (k.mask_bits && k.out_bits)) return -1;
+  if (r.bits) {
     if constexpr ((K == 128 || K == 256) && NH == 256) {
-      if (k.out_bits) return (m || k.act != GPV_ACT_RELU) ? -1 : c1s_launch<K, NH, true, false, false, false, true>(k, st);
-      return c1s_launch<K, NH, true, true, false, false, true>(k, st);
+      return m ? c1s_launch_p<K, NH, true, true, false, false, true>(k, r, st) : c1s_launch_p<K, NH, true, false, false, false, true>(k, r, st);
     } else if constexpr (K == 512 && NH == 128) {
-      if (k.out_bits) return -1;
-      return c1s_launch<K, NH, true, true, false, false, true>(k, st);
+      return c1s_launch_p<K, NH, true, true, false, false, true>(k, r, st);
     } else {
       return -1;
     }
   }
-  if (nt) {      // (non-temporal: the layer1 forwards -- never with a mask)
-    if (m) return -1;
-    return r ? c1s_launch<K, NH, true, false, true>(k, st) : c1s_launch<K, NH, false, false, true>(k, st);
-  }
-  if (r && m) return c1s_launch<K, NH, true, true, false>(k, st);
-  if (r) return c1s_launch<K, NH, true, false, false>(k, st);
-  if (m) return c1s_launch<K, NH, false, true, false>(k, st);
-  return c1s_launch<K, NH, false, false, false>(k, st);
+  if (r.nt) return res ? c1s_launch_p<K, NH, true, false, true>(k, r, st) : c1s_launch_p<K, NH, false, false, true>(k, r, st);
+  if (res && m) return c1s_launch_p<K, NH, true, true, false>(k, r, st);
+  if (res) return c1s_launch_p<K, NH, true, false, false>(k, r, st);
+  if (m) return c1s_launch_p<K, NH, false, true, false>(k, r, st);
+  return c1s_launch_p<K, NH, false, false, false>(k, r, st);
 }
 
 template <int K>
-int c1s_n(const GemmK& k, hipStream_t st, bool linear) {
-  switch (c1s_cols(K, k.N)) {          // channels per block -> channels per register pass
-    case 64: return c1s_flags<K, 64>(k, st, linear);
-    case 128: return c1s_flags<K, 128>(k, st, linear);
-    case 256: case 512: if constexpr (K <= 256) return c1s_flags<K, 256>(k, st, linear); else return -1;
+int c1s_n(const GemmK& k, const Route& r, hipStream_t st) {
+  switch (r.nh) {          // channels per register pass
+    case 64: return c1s_flags<K, 64>(k, r, st);
+    case 128: return c1s_flags<K, 128>(k, r, st);
+    case 256: if constexpr (K <= 256) return c1s_flags<K, 256>(k, r, st); else return -1;
   }
   return -1;
 }
 
 }  // namespace
 
-int g_c1s_mode = 1;          // 0 never, 1 heuristic, 2 wherever legal (tests)
-long g_c1s_launches = 0;     // gpv_set_option(GPV_OPT_C1S_LAUNCHES, .)
-
-// 0 = launched, -1 = not applicable, > 0 = hipError_t
-int c1s_try_launch(const GemmK& k, int dtype_in, int dtype_out, hipStream_t st, bool linear, bool dry) {
-  static const int env = tune_env("GPV_C1S", -1);
-  const int mode = env >= 0 ? env : g_c1s_mode;
-  if (mode == 0 || dtype_in != GPV_BF16 || dtype_out != GPV_BF16) return -1;
-  if (k.K != 64 && k.K != 128 && k.K != 256 && k.K != 512) return -1;
-  if (k.N != 64 && k.N != 128 && k.N != 256 && k.N != 512 && k.N != 1024 && k.N != 2048 && !(linear && k.N % 256 == 0 && k.N <= 2048)) return -1;
-  const int ncols = c1s_cols(k.K, k.N), nsl = k.N / ncols;
-  if ((size_t)ncols * (k.K + 8) * 2 + (size_t)ncols * 4 > 150 * 1024 || nsl > 8) return -1;
-  if (k.rowscale || k.accumulate || k.split_k > 1 || k.a_rowsum) return -1;
-  if ((k.alpha != 1.0f || k.dthresh) && !(linear && k.K == 256 && k.N >= 256 && k.N % 256 == 0)) return -1;
-  if (linear && (k.cg.SH == 2 || k.cg.cm || k.nt_io)) return -1;
-  if (k.act != GPV_ACT_NONE && k.act != GPV_ACT_RELU) return -1;
-  if (k.lda % 8 || k.ldb != k.K || k.ldc % 8 || (k.res && k.ldr % 8) || (k.mask && k.ldm % 8)) return -1;
-  if (!al16(k.A) || !al16(k.B) || !al16(k.C) || (k.res && !al16(k.res)) || (k.mask && !al16(k.mask))) return -1;
-  if (linear) {      // gpv_gemm: 256 -> 2048 features over >= 2048 rows (the DETR feed-forward; tools/bench_c1s_linear.py: 1024 / 1536 outputs are faster on the tile kernels)
-    if (mode == 1 && (k.K != 256 || k.N < 1536 || k.M < 2048)) return -1;      // (1536: as graph nodes 20.8 against 26.8 us at 9600 rows, tools/tune_gemms.py --chain; 1024 stays on the tile kernels)
-  } else if (mode == 1 && ((int64_t)k.M * nsl < 65536 || k.M < 32768)) return -1;   // a streaming regime needs rows (x slices): the layer1-3 maps at training batch sizes
-  if (k.mask_bits || k.out_bits) {
-    // instances that exist with mask bits (c1s_flags) -- decided here so that a dry run (gpv_conv2d_mask_bits_ok) answers what a launch would do
-    const int nh = ncols >= 256 ? 256 : ncols;
-    const bool inst = ((k.K == 128 || k.K == 256) && nh == 256) || (k.K == 512 && nh == 128 && !k.out_bits);
-    if (linear || !inst || !k.res || k.nt_io || (k.mask_bits && k.out_bits) || k.N % 256 != 0 || (k.out_bits && (k.mask && !k.mask_bits))) return -1;
-    if (k.out_bits && k.act != GPV_ACT_RELU) return -1;
-    if (k.K <= 128 && ncols / nh > 2) return -1;
-    if (k.K > 128 && ncols / nh != 1) return -1;
-  }
-  if (dry) return 0;
+int c1s_launch(const GemmK& k, const Route& r, hipStream_t st) {
   int e = -1;
-  switch (k.K) {
-    case 64: e = c1s_n<64>(k, st, linear); break;
-    case 128: e = c1s_n<128>(k, st, linear); break;
-    case 256: e = c1s_n<256>(k, st, linear); break;
-    case 512: e = c1s_n<512>(k, st, linear); break;       // (N <= 128: the weights must fit the LDS)
+  switch (r.ck) {
+    case 64: e = c1s_n<64>(k, r, st); break;
+    case 128: e = c1s_n<128>(k, r, st); break;
+    case 256: e = c1s_n<256>(k, r, st); break;
+    case 512: e = c1s_n<512>(k, r, st); break;
   }
-  if (e == 0) ++g_c1s_launches;
-  return e;
+  if (e == 0) ++g_knobs.n_c1s;
+  return e < 0 ? (int)hipErrorInvalidValue : e;
 }
 
 }  // namespace gpvk

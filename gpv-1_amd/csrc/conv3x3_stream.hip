@@ -26,8 +26,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int C3_OOB = 0x7ffffff0;
-constexpr int C3_NSL = 64;              // output channels per block
 
 // MFMA row m (0..31) of a 32-channel tile <-> channel offset: lane half h = (m >> 2) & 1 owns rows 8 q + 4 h + j, which must be
 // the channels 16 (q >> 1) + 8 h + 4 (q & 1) + j (two runs of 8 consecutive channels per lane): swap bits 2 and 3 of m
@@ -213,43 +211,30 @@ void c3r_kernel(GemmK p, int rows_per_item, int nstrip, int nseg, int nitems) {
   }
 }
 
-template <int CIN, bool DGRAD, bool MASK, int WAVES>
-int c3r_launch_w(const GemmK& k, hipStream_t st) {
-  constexpr int KP = 9 * CIN + 8;
-  const size_t lds = (size_t)C3_NSL * KP * 2 + C3_NSL * sizeof(float);
-  auto fn = c3r_kernel<CIN, DGRAD, MASK, WAVES>;
-  static bool attr = false;
+// launch tail of both streaming 3x3 kernels: geometry and work-item arguments as gemm_route.h c3s_select fixed them
+template <typename F>
+int c3_launch_fn(F fn, bool& attr, const GemmK& k, const Route& r, hipStream_t st) {
   if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
     if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }      // (leave no stale error behind for the next launch check)
     attr = true;
   }
-  const ConvGeom& g = k.cg;
-  const int nsl = k.N / C3_NSL, Bn = k.M / (g.OH * g.OW);
-  const int nstrip = (g.OW + 29) / 30;
-  static const int env_blocks = tune_env("GPV_C3S_BLOCKS", 0);
-  static const int env_rows = tune_env("GPV_C3R_ROWS", 0);
-  int blocks = env_blocks > 0 ? env_blocks : ((CIN == 64 ? 512 : 256) / nsl);
-  // rows per item: a multiple of 3 such that the items fill the resident waves about twice (each segment re-reads two halo rows)
-  int rows = env_rows > 0 ? env_rows : 3;
-  if (env_rows <= 0) {
-    const int64_t waves = (int64_t)blocks * WAVES;
-    while (rows < 30 && (int64_t)Bn * nstrip * ((g.OH + rows + 2) / (rows + 3)) >= 2 * waves) rows += 3;
-  }
-  const int nseg = (g.OH + rows - 1) / rows;
-  const int nitems = Bn * nstrip * nseg;
-  while (blocks > 8 && (int64_t)(blocks - 8) * WAVES >= nitems) blocks -= 8;
-  hipLaunchKernelGGL(fn, dim3(blocks, nsl), dim3(WAVES * 64), lds, st, k, rows, nstrip, nseg, nitems);
+  hipLaunchKernelGGL(fn, dim3(r.gx, r.gy), dim3(r.block), (size_t)r.lds, st, k, r.rows, r.nstrip, r.nseg, r.nitems);
   GPV_CHECK_LAUNCH();
   return 0;
 }
 
+template <int CIN, bool DGRAD, bool MASK, int WAVES>
+int c3r_launch_w(const GemmK& k, const Route& r, hipStream_t st) {
+  static bool attr = false;
+  return c3_launch_fn(c3r_kernel<CIN, DGRAD, MASK, WAVES>, attr, k, r, st);
+}
+
 template <int CIN, bool DGRAD, bool MASK>
-int c3r_launch(const GemmK& k, hipStream_t st) {
-  static const int env_waves = tune_env("GPV_C3S_WAVES", 0);
-  if (env_waves == 4) return c3r_launch_w<CIN, DGRAD, MASK, 4>(k, st);
-  if (env_waves == 16) return c3r_launch_w<CIN, DGRAD, MASK, 16>(k, st);
-  return c3r_launch_w<CIN, DGRAD, MASK, 8>(k, st);
+int c3r_launch(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.waves == 4) return c3r_launch_w<CIN, DGRAD, MASK, 4>(k, r, st);
+  if (r.waves == 16) return c3r_launch_w<CIN, DGRAD, MASK, 16>(k, r, st);
+  return c3r_launch_w<CIN, DGRAD, MASK, 8>(k, r, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -400,74 +385,25 @@ __global__ __launch_bounds__(WAVES * 64) void c3d2_kernel(GemmK p, int rows_per_
 }
 
 template <int CIN, bool MASK, bool BITS = false>
-int c3d2_launch(const GemmK& k, hipStream_t st) {
-  constexpr int WAVES = 8, KP = 9 * CIN + 8;
-  const size_t lds = (size_t)C3_NSL * KP * 2;
-  auto fn = c3d2_kernel<CIN, MASK, WAVES, BITS>;
+int c3d2_launch(const GemmK& k, const Route& r, hipStream_t st) {
   static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }      // (leave no stale error behind for the next launch check)
-    attr = true;
-  }
-  const ConvGeom& g = k.cg;
-  const int nsl = k.N / C3_NSL, Bn = k.M / (g.OH * g.OW);
-  const int nstrip = (g.IW + 30) / 31;
-  static const int env_rows = tune_env("GPV_C3D2_ROWS", 0);
-  int blocks = 256 / nsl;
-  int rows = env_rows > 0 ? env_rows : 2;
-  if (env_rows <= 0) {
-    const int64_t waves = (int64_t)blocks * WAVES;
-    while (rows < 16 && (int64_t)Bn * nstrip * ((g.IH + rows + 1) / (rows + 2)) >= 2 * waves) rows += 2;
-  }
-  const int nseg = (g.IH + rows - 1) / rows;
-  const int nitems = Bn * nstrip * nseg;
-  while (blocks > 8 && (int64_t)(blocks - 8) * WAVES >= nitems) blocks -= 8;
-  hipLaunchKernelGGL(fn, dim3(blocks, nsl), dim3(WAVES * 64), lds, st, k, rows, nstrip, nseg, nitems);
-  GPV_CHECK_LAUNCH();
-  return 0;
+  return c3_launch_fn(c3d2_kernel<CIN, MASK, 8, BITS>, attr, k, r, st);
 }
 
 template <int CIN>
-int c3r_mode(const GemmK& k, bool dgrad, hipStream_t st) {
-  const bool m = k.mask != nullptr;
-  if (dgrad) return m ? c3r_launch<CIN, true, true>(k, st) : c3r_launch<CIN, true, false>(k, st);
-  return m ? c3r_launch<CIN, false, true>(k, st) : c3r_launch<CIN, false, false>(k, st);
+int c3r_mode(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.dgrad) return r.mask ? c3r_launch<CIN, true, true>(k, r, st) : c3r_launch<CIN, true, false>(k, r, st);
+  return r.mask ? c3r_launch<CIN, false, true>(k, r, st) : c3r_launch<CIN, false, false>(k, r, st);
 }
 
 }  // namespace
 
-int g_c3s_mode = 1;          // 0 never, 1 heuristic, 2 wherever legal (tests)
-long g_c3s_launches = 0;
-
-// k: the GemmK gpv_conv2d prepared for the implicit-GEMM path (A = input pixels, B = [N][9][Cin] weights, cg = geometry).
-// 0 = launched, -1 = not applicable, > 0 = hipError_t
-int c3s_try_launch(const GemmK& k, int dtype_in, int dtype_out, hipStream_t st, bool dry) {
-  static const int env = tune_env("GPV_C3S", -1);
-  const int mode = env >= 0 ? env : g_c3s_mode;
-  const ConvGeom& g = k.cg;
-  if (mode == 0 || dtype_in != GPV_BF16 || dtype_out != GPV_BF16) return -1;
-  if (g.KH != 3 || g.KW != 3 || g.PH != 1 || g.PW != 1 || g.SH != g.SW) return -1;
-  if ((g.Cin != 64 && g.Cin != 128) || k.N % C3_NSL != 0 || k.N > 256 || k.K != 9 * g.Cin) return -1;
-  if (g.Cs % 8 != 0 || k.ldc % 8 != 0 || (k.mask && k.ldm % 8 != 0) || k.ldb != k.K) return -1;
-  if (k.res || k.rowscale || k.alpha != 1.0f || k.dthresh || k.accumulate || k.split_k > 1 || k.a_rowsum) return -1;
-  if (k.act != GPV_ACT_NONE && k.act != GPV_ACT_RELU) return -1;
-  if (!al16(k.A) || !al16(k.B) || !al16(k.C) || (k.mask && !al16(k.mask))) return -1;
-  const bool d2 = g.SH == 2 && g.dgrad && g.Cin == 128 && g.OH == 2 * g.IH && g.OW == 2 * g.IW && k.act == GPV_ACT_NONE && !k.bias;
-  if (g.SH != 1 && !d2) return -1;       // (the stride-2 forward stays on the tile kernels)
-  // input extent addressed with 32-bit byte offsets (dgrad: the "input" is dy)
-  const int64_t in_px = (int64_t)(k.M / (g.OH * g.OW)) * g.IH * g.IW;
-  if (in_px * g.Cs * 2 >= (int64_t)C3_OOB) return -1;
-  // a streaming regime needs rows: the layer1 / layer2 maps at training batch sizes -- and layer1's 64-channel map of ONE image (19200
-  // pixels, forward): 12.4 us as a graph node against 15.2 for the 64 x 64 tile kernel (tools/bench_c3_bs1.py); layer2's 4800 pixels: 20.9 against 18.2
-  if (mode == 1 && k.M < 65536 && !(g.Cin == 64 && !g.dgrad && k.M >= 16384)) return -1;
-  if (k.out_bits || (k.mask_bits && !(d2 && k.N == 128 && (reinterpret_cast<uintptr_t>(k.mask_bits) & 15) == 0))) return -1;      // mask bits: the stride-2 backward-data over 128 channels only
-  if (dry) return 0;
+int c3s_launch(const GemmK& k, const Route& r, hipStream_t st) {
   int e;
-  if (d2 && k.mask_bits) e = c3d2_launch<128, true, true>(k, st);
-  else if (d2) e = k.mask ? c3d2_launch<128, true>(k, st) : c3d2_launch<128, false>(k, st);
-  else e = g.Cin == 64 ? c3r_mode<64>(k, g.dgrad != 0, st) : c3r_mode<128>(k, g.dgrad != 0, st);
-  if (e == 0) ++g_c3s_launches;
+  if (r.d2 && r.bits) e = c3d2_launch<128, true, true>(k, r, st);
+  else if (r.d2) e = r.mask ? c3d2_launch<128, true>(k, r, st) : c3d2_launch<128, false>(k, r, st);
+  else e = r.ck == 64 ? c3r_mode<64>(k, r, st) : c3r_mode<128>(k, r, st);
+  if (e == 0) ++g_knobs.n_c3s;
   return e;
 }
 

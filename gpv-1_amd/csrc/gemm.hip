@@ -23,9 +23,6 @@ using namespace gpvk;
 
 namespace {
 
-constexpr int BK = 32;
-constexpr int LDK = 40;  // LDS row pitch in elements (80 B: keeps ds_read_b128 16-B aligned, spreads banks)
-
 // ---- 8 staged elements of one operand row -------------------------------------------------
 template <typename T> struct Raw8;
 __device__ __forceinline__ uint32_t bf_bits(float x) { return (uint32_t)__builtin_bit_cast(unsigned short, (bf16)x); }
@@ -745,56 +742,43 @@ int launch_splitk_reduce(const float* ws, int split, int M, int N, float* C, int
 namespace {
 
 template <typename TIn, typename TOut, int AMODE, int BMODE, int BM, int BN, bool VEC>
-int launch_cfg_v(const GemmK& k, int batch, hipStream_t st) {
+int launch_cfg_v(const GemmK& k, const Route& r, hipStream_t st) {
   constexpr bool PRECISE = sizeof(TIn) == 4;
   constexpr size_t lds = (size_t)2 * (BM + BN) * LDK * 2 * (PRECISE ? 2 : 1);
   GemmK p = k;
-  const int tilesM = (p.M + BM - 1) / BM;
-  p.tilesN = (p.N + BN - 1) / BN;
-  const int kt_total = (p.K + BK - 1) / BK;
-  int split = p.split_k < 1 ? 1 : p.split_k;
-  if (split > kt_total) split = kt_total;
-  p.kt_per_split = (kt_total + split - 1) / split;
-  split = (kt_total + p.kt_per_split - 1) / p.kt_per_split;
-  // Split reduction without atomics when the caller lent a workspace: every split writes its partial [M,N] product
-  // with the normal coalesced epilogue, a second tiny kernel adds the slabs to C.  fp32 atomics on C cost
-  // outputs x splits / ~94e9 s (67 us for the 128x512 gradient of a layer2 1x1 conv at its best split of 96).
+  p.tilesN = r.tilesN;
+  p.kt_per_split = r.kt_per_split;
   p.ws = nullptr;
-  bool two_pass = false;
-  if (p.accumulate && split > 1 && batch == 1 && k.ws_base != nullptr && sizeof(TOut) == 4 &&
-      (int64_t)split * p.M * p.N * 4 <= k.ws_bytes && p.N % 4 == 0 && p.ldc % 4 == 0 &&
-      (reinterpret_cast<uintptr_t>(p.C) & 15) == 0) {
-    two_pass = true;
+  if (r.two_pass) {       // split reduction through the workspace (gemm_route.h tile_geometry): plain partial products, a second kernel adds the slabs to C
     p.ws = reinterpret_cast<float*>(k.ws_base);
     p.accumulate = 0; p.res = nullptr; p.mask = nullptr; p.bias = nullptr; p.act = 0; p.dthresh = 0;
   }
   auto fn = gemm_kernel<TIn, TOut, AMODE, BMODE, BM, BN, VEC>;
   if constexpr (AMODE == OP_PLAIN && BMODE == OP_PLAIN) {
-    if (k.conv1x1) fn = conv1x1_kernel<TIn, TOut, BM, BN, VEC>;
+    if (r.c11) fn = conv1x1_kernel<TIn, TOut, BM, BN, VEC>;
     if constexpr (std::is_same<TIn, bf16>::value && std::is_same<TOut, bf16>::value && VEC) {
-      if (k.conv1x1 && k.nt_io && !p.dthresh && !two_pass) fn = conv1x1_nt_kernel<BM, BN>;
+      if (r.nt) fn = conv1x1_nt_kernel<BM, BN>;
     }
   }
   static bool attr_done[2] = {false, false};
-  if (lds > 64 * 1024 && !attr_done[k.conv1x1 ? 1 : 0]) {
+  if (lds > 64 * 1024 && !attr_done[r.c11 ? 1 : 0]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }      // (leave no stale error behind for the next launch check)
-    attr_done[k.conv1x1 ? 1 : 0] = true;
+    attr_done[r.c11 ? 1 : 0] = true;
   }
-  dim3 grid(tilesM * p.tilesN, split, batch);
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, p);
+  hipLaunchKernelGGL(fn, dim3(r.gx, r.gy, r.gz), dim3(r.block), lds, st, p);
   GPV_CHECK_LAUNCH();
-  if (two_pass) {
-    const int e = launch_splitk_reduce(p.ws, split, p.M, p.N, reinterpret_cast<float*>(p.C), p.ldc, st);
+  if (r.two_pass) {
+    const int e = launch_splitk_reduce(p.ws, r.split, p.M, p.N, reinterpret_cast<float*>(p.C), p.ldc, st);
     if (e) return e;
   }
   return 0;
 }
 
 template <typename TIn, typename TOut, int AMODE, int BMODE, int BM, int BN>
-int launch_cfg(const GemmK& k, int batch, hipStream_t st) {
-  if (k.vecA && k.vecB) return launch_cfg_v<TIn, TOut, AMODE, BMODE, BM, BN, true>(k, batch, st);
-  return launch_cfg_v<TIn, TOut, AMODE, BMODE, BM, BN, false>(k, batch, st);
+int launch_cfg(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.vec) return launch_cfg_v<TIn, TOut, AMODE, BMODE, BM, BN, true>(k, r, st);
+  return launch_cfg_v<TIn, TOut, AMODE, BMODE, BM, BN, false>(k, r, st);
 }
 
 // Second pass of a split FORWARD convolution: y[m, n] = act(sum_s ws[s][m][n] + bias[n] + res[m, n]), four columns per thread.
@@ -826,68 +810,50 @@ __global__ __launch_bounds__(256) void conv_split_epilogue_kernel(const float* _
   *reinterpret_cast<bf16x4*>(y + off) = out;
 }
 
-// Forward convolutions over a few hundred to a few thousand output pixels (inference at batch 1: layer2-4 see 4800 / 1200 / 300
-// pixels): 12..40 tiles of a 128-wide kernel walk K = 1152..4608 alone on a 256-CU chip.  The reduction is split over grid.y
-// into fp32 slabs of the caller's workspace (64 x 64 tiles, ~300 workgroups of >= 8 k-tiles), a second launch sums the slabs and
-// applies bias / residual / ReLU.  Returns 0 = launched, -1 = not applicable.
-int conv_split_try_launch(const GemmK& k, int dtype_in, int dtype_out, hipStream_t st) {
-  static const int on = tune_env("GPV_CONV_SPLIT", 1);
-  if (!on || g_kernel_forced || dtype_in != GPV_BF16 || dtype_out != GPV_BF16 || !k.vecA || !k.vecB || !k.ws_base) return -1;
-  if (k.mask || k.rowscale || k.dthresh || k.accumulate || k.cg.dgrad || k.alpha != 1.0f || (k.act != 0 && k.act != GPV_ACT_RELU)) return -1;
-  if (k.N % 4 != 0 || k.ldc != k.N || (k.res && k.ldr != k.N) || !al16(k.C) || (k.res && !al16(k.res)) || (k.bias && !al16(k.bias))) return -1;
-  const int tiles = ((k.M + 63) / 64) * ((k.N + 63) / 64);
-  const int kt_total = (k.K + BK - 1) / BK;
-  if (tiles > 160 || kt_total < 32) return -1;
-  int split = (384 + tiles - 1) / tiles;
-  if (split > kt_total / 8) split = kt_total / 8;
-  if (split > 16) split = 16;
-  while (split > 1 && (int64_t)split * k.M * k.N * 4 > k.ws_bytes) --split;
-  if (split < 2) return -1;
+// FAM_CONV_SPLIT (gemm_route.h conv_split_select): the reduction split over grid.y into fp32 slabs of the caller's workspace, then the
+// epilogue kernel above
+int conv_split_launch(const GemmK& k, const Route& r, hipStream_t st) {
   GemmK p = k;
-  p.tilesN = (p.N + 63) / 64;
-  p.kt_per_split = (kt_total + split - 1) / split;
-  split = (kt_total + p.kt_per_split - 1) / p.kt_per_split;
-  p.split_k = split;
+  p.tilesN = r.tilesN;
+  p.kt_per_split = r.kt_per_split;
+  p.split_k = r.split;
   p.ws = reinterpret_cast<float*>(k.ws_base);
   p.res = nullptr; p.bias = nullptr; p.act = 0;
-  constexpr size_t lds = (size_t)2 * (64 + 64) * LDK * 2;
-  hipLaunchKernelGGL((gemm_kernel<bf16, float, OP_CONV, OP_PLAIN, 64, 64, true>), dim3(tiles, split, 1), dim3(256), lds, st, p);
+  hipLaunchKernelGGL((gemm_kernel<bf16, float, OP_CONV, OP_PLAIN, 64, 64, true>), dim3(r.gx, r.gy, r.gz), dim3(r.block), (size_t)r.lds, st, p);
   GPV_CHECK_LAUNCH();
   const int64_t quads = (int64_t)k.M * (k.N / 4);
-  hipLaunchKernelGGL(conv_split_epilogue_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, p.ws, split, k.M, k.N, k.bias,
+  hipLaunchKernelGGL(conv_split_epilogue_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, p.ws, r.split, k.M, k.N, k.bias,
                      reinterpret_cast<const bf16*>(k.res), k.act, reinterpret_cast<bf16*>(k.C));
   GPV_CHECK_LAUNCH();
   return 0;
 }
 
 template <typename TIn, typename TOut, int AMODE, int BMODE>
-int launch_tiles(const GemmK& k, int batch, hipStream_t st) {
-  const int64_t sk = (k.split_k < 1 ? 1 : k.split_k);
-  const int64_t t128 = (int64_t)((k.M + 127) / 128) * ((k.N + 127) / 128) * batch * sk;
-  const int64_t t12864 = (int64_t)((k.M + 127) / 128) * ((k.N + 63) / 64) * batch * sk;
-  static const int force = tune_env("GPV_FORCE_TILE", 0);   // tuning only
-  int cfg;   // 0: 128x128, 1: 128x64, 2: 64x64
-  if (force) cfg = force - 1;
-  else if (k.K <= 256) cfg = (k.N >= 1024 && t128 >= 384 && !k.conv1x1) ? 0 : 2;   // <= 8 k-tiles: HBM/latency bound, 64x64 keeps more bytes in flight
-                                                                      // (tools/bench_c3.py); the wide Linear outputs (FFN expansion) stay at 128x128, the
-                                                                      // 1x1 convs since the buffer-load loaders do not: layer3 conv3 66 -> 61, conv1 dgrad 78 -> 65 us
-  else if (k.N <= 64 && t12864 >= 384) cfg = 1;                       // N = 64 (layer1): 128x64, measured 100 vs 105 / 144 vs 151 us
-  else if (k.N > 64 && t128 >= 384) cfg = 0;
-  else if (t12864 >= 384) cfg = 1;
-  else cfg = 2;
-  if (cfg == 0) return launch_cfg<TIn, TOut, AMODE, BMODE, 128, 128>(k, batch, st);
-  if (cfg == 1) return launch_cfg<TIn, TOut, AMODE, BMODE, 128, 64>(k, batch, st);
-  return launch_cfg<TIn, TOut, AMODE, BMODE, 64, 64>(k, batch, st);
+int launch_tiles(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.bm == 128 && r.bn == 128) return launch_cfg<TIn, TOut, AMODE, BMODE, 128, 128>(k, r, st);
+  if (r.bm == 128) return launch_cfg<TIn, TOut, AMODE, BMODE, 128, 64>(k, r, st);
+  return launch_cfg<TIn, TOut, AMODE, BMODE, 64, 64>(k, r, st);
 }
 
 template <int AMODE, int BMODE>
-int launch_dtype(const GemmK& k, int batch, int dt_in, int dt_out, hipStream_t st) {
-  if (dt_in == GPV_BF16 && dt_out == GPV_BF16) return launch_tiles<bf16, bf16, AMODE, BMODE>(k, batch, st);
+int launch_dtype(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.dt_in == GPV_BF16 && r.dt_out == GPV_BF16) return launch_tiles<bf16, bf16, AMODE, BMODE>(k, r, st);
 #ifndef GPV_EXPERIMENT      /* trimmed instantiation set for kernel-tuning builds */
-  if (dt_in == GPV_BF16 && dt_out == GPV_F32) return launch_tiles<bf16, float, AMODE, BMODE>(k, batch, st);
-  if (dt_in == GPV_F32 && dt_out == GPV_F32) return launch_tiles<float, float, AMODE, BMODE>(k, batch, st);
+  if (r.dt_in == GPV_BF16 && r.dt_out == GPV_F32) return launch_tiles<bf16, float, AMODE, BMODE>(k, r, st);
+  if (r.dt_in == GPV_F32 && r.dt_out == GPV_F32) return launch_tiles<float, float, AMODE, BMODE>(k, r, st);
 #endif
   return (int)hipErrorInvalidValue;
+}
+
+// FAM_TILE: the register-staged kernel
+int tile_launch(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.bmode == OP_CONV) {       // conv weight gradient: bf16 on three tiles, fp32 ("precise") on 64 x 64
+    if (r.dt_in == GPV_BF16) return launch_tiles<bf16, float, OP_TRANS, OP_CONV>(k, r, st);
+    return launch_cfg<float, float, OP_TRANS, OP_CONV, 64, 64>(k, r, st);
+  }
+  if (r.amode == OP_CONV) return launch_dtype<OP_CONV, OP_PLAIN>(k, r, st);
+  if (r.amode == OP_TRANS) return launch_dtype<OP_TRANS, OP_TRANS>(k, r, st);
+  return r.bmode == OP_TRANS ? launch_dtype<OP_PLAIN, OP_TRANS>(k, r, st) : launch_dtype<OP_PLAIN, OP_PLAIN>(k, r, st);
 }
 
 // Backward-data of a 1x1 stride-2 convolution (the downsample projections): only output pixels with even row AND column receive a
@@ -917,266 +883,84 @@ __global__ __launch_bounds__(256) void s2_dgrad_fill_kernel(bf16* __restrict__ d
 
 extern "C" int gpv_abi_version(void) { return 2; }
 
-extern "C" int gpv_gemm(const gpv_gemm_args* a, void* stream) {
-  if (!a || !a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch <= 0) return (int)hipErrorInvalidValue;
-  if ((a->split_k > 1 || a->accumulate) && a->dtype_out != GPV_F32) return (int)hipErrorInvalidValue;
-  if (a->split_k > 1 && (!a->accumulate || a->bias || a->res || a->act || a->relu_mask || a->drop_p > 0.f)) return (int)hipErrorInvalidValue;
-  GemmK k{};
-  k.A = a->A; k.B = a->B; k.C = a->C; k.M = a->M; k.N = a->N; k.K = a->K;
-  k.lda = a->lda; k.ldb = a->ldb; k.ldc = a->ldc; k.sA = a->sA; k.sB = a->sB; k.sC = a->sC;
-  k.alpha = a->alpha; k.rowscale = a->rowscale; k.bias = a->bias;
-  k.res = a->res; k.ldr = a->ldr; k.sR = a->sR; k.mask = a->relu_mask; k.ldm = a->ldm;
-  k.act = a->act; k.seed = a->seed; k.seed_dev = gpvk::g_seed_dev;
-  k.dthresh = a->drop_p > 0.f ? drop_thresh(a->drop_p) : 0u;
-  k.dscale = a->drop_p > 0.f ? 1.0f / (1.0f - a->drop_p) : 1.0f;
-  k.accumulate = a->accumulate; k.split_k = a->split_k;
-  k.a_rowsum = a->a_rowsum;
-  k.no_small = (a->flags & GPV_GEMM_NO_PIPE_SMALL) ? 1 : 0;
-  k.ws_base = a->workspace; k.ws_bytes = a->workspace ? a->workspace_bytes : 0;
-  if (k.a_rowsum && !(a->layoutA == GPV_TRANS && a->layoutB == GPV_TRANS && a->batch == 1)) return (int)hipErrorInvalidValue;
-  if (a->accumulate && a->split_k <= 1 && !a->res) {
-    // one block owns every output element: C += acc as a coalesced read-modify-write through the LDS epilogue
-    // (fp32 atomics run at ~70 G/s: a 10000x768 gradient costs 110 us in atomics alone)
-    k.accumulate = 0; k.res = a->C; k.ldr = a->ldc; k.sR = a->sC;
-  }
-  const int esz = a->dtype_in == GPV_F32 ? 4 : 2;
-  const int64_t vecel = 16 / esz;  // elements per 16 B
-  auto vec_ok = [&](const void* ptr, int64_t ld, int64_t bs, int layout, int extent_contig) {
-    bool ok = al16(ptr) && (ld % vecel == 0) && (a->batch == 1 || bs % vecel == 0);
-    // 16-byte chunks: the contiguous extent must be a multiple of 8, or end inside the row pitch -- a reduction-major
-    // operand's last chunk then only feeds outputs beyond M / N (discarded); a k-major operand's last chunk multiplies
-    // masked rows of the other operand, so its padding must be finite (caller's promise: GPV_GEMM_KPAD_FINITE)
-    if (layout == GPV_KMAJOR) ok = ok && (a->K % 8 == 0 || ((a->flags & GPV_GEMM_KPAD_FINITE) && ld >= ((int64_t)a->K + 7) / 8 * 8));
-    else ok = ok && (extent_contig % 8 == 0 || ld >= ((int64_t)extent_contig + 7) / 8 * 8);
-    return ok ? 1 : 0;
-  };
-  k.vecA = vec_ok(a->A, a->lda, a->sA, a->layoutA, a->M);
-  k.vecB = vec_ok(a->B, a->ldb, a->sB, a->layoutB, a->N);
-  {   // the 16-byte path addresses an operand (one batch element) with 32-bit byte offsets
-    const int64_t lim = 0x7ffffff0ll / esz;
-    if ((int64_t)(a->layoutA == GPV_KMAJOR ? a->M : a->K) * a->lda >= lim) k.vecA = 0;
-    if ((int64_t)(a->layoutB == GPV_KMAJOR ? a->N : a->K) * a->ldb >= lim) k.vecB = 0;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int la = a->layoutA, lb = a->layoutB;
-  if (la == GPV_KMAJOR && lb == GPV_KMAJOR) {
-    const int gv = gemv_try_launch(k, a->dtype_in, a->dtype_out, a->batch, st);                // M <= 8: matrix-vector products of the decode step
-    if (gv >= 0) return gv;
-    static const bool c1s_linear = tune_env("GPV_C1S_LINEAR", 1) != 0;     // 0: A/B only
-    if (a->batch == 1 && !g_kernel_forced && c1s_linear) {
-      const int cs = c1s_try_launch(k, a->dtype_in, a->dtype_out, st, true);               // K = 256 -> >= 1024 features: weights resident in LDS, rows streamed
-      if (cs >= 0) return cs;
-    }
-    const int pp = pipe_try_launch(k, OP_PLAIN, a->dtype_in, a->dtype_out, a->batch, st);     // pipelined direct-to-LDS kernel (big tiles, and the small-M 6-8 stage tiles)
-    if (pp >= 0) return pp;
-    const int sk = skinny_try_launch(k, 0, a->dtype_in, a->dtype_out, a->batch, st);             // few tiles, long reduction: what the pipelined kernel does not take (fp32 outputs, ragged N)
-    if (sk >= 0) return sk;
-    const int g = glds_try_launch(k, OP_PLAIN, a->dtype_in, a->dtype_out, a->batch, st);      // 8-wave direct-to-LDS kernel when it qualifies
-    if (g >= 0) return g;
-    return launch_dtype<OP_PLAIN, OP_PLAIN>(k, a->batch, a->dtype_in, a->dtype_out, st);
-  }
-  if (la == GPV_KMAJOR && lb == GPV_TRANS) {
-    const int sk = skinny_try_launch(k, 1, a->dtype_in, a->dtype_out, a->batch, st);             // small backward-data GEMMs
-    if (sk >= 0) return sk;
-    return launch_dtype<OP_PLAIN, OP_TRANS>(k, a->batch, a->dtype_in, a->dtype_out, st);
-  }
-  if (la == GPV_TRANS && lb == GPV_TRANS) {
-    if (a->accumulate) {                                  // small weight gradients: reduction split over the block's waves
-      GemmK kk = k;
-      kk.accumulate = 1; kk.res = nullptr; kk.ldr = 0; kk.sR = 0;      // (the split==1 rewrite above turned C += into res = C)
-      const int gt = glds_tt_try_launch(kk, a->dtype_in, a->dtype_out, a->batch, st);        // 128-multiples, long reduction
-      if (gt >= 0) return gt;
-      const int sk = skinny_tt_try_launch(kk, a->dtype_in, a->dtype_out, a->batch, st);
-      if (sk >= 0) return sk;
-    }
-    return launch_dtype<OP_TRANS, OP_TRANS>(k, a->batch, a->dtype_in, a->dtype_out, st);
-  }
-  return (int)hipErrorInvalidValue;
-}
+namespace gpvk { Knobs g_knobs; }
+static_assert(kRouteInvalid == (int)hipErrorInvalidValue, "gemm_route.h names hipErrorInvalidValue by its value");
 
-// dry: check only (gpv_conv2d_mask_bits_ok) -- valid for calls that ask for mask bits, which return before any other launch path
-static int conv2d_impl(const gpv_conv_args* a, hipStream_t st, bool dry) {
-  if (!a || !a->x || !a->w || !a->y) return (int)hipErrorInvalidValue;
-  if (a->Cin % 32 != 0) return (int)hipErrorInvalidValue;
-  if ((a->SH != 1 && a->SH != 2) || (a->SW != 1 && a->SW != 2)) return (int)hipErrorInvalidValue;
-  const bool want_bits = a->y_mask_bits != nullptr || a->relu_mask_bits != nullptr;
-  if (want_bits) {
-    // one-bit ReLU masks: the streaming 1x1 kernel only (stride 1, pointwise), forward with ReLU writes them, backward-data reads them
-    const bool pw1 = a->KH == 1 && a->KW == 1 && a->SH == 1 && a->SW == 1 && a->PH == 0 && a->PW == 0 && a->IH == a->OH && a->IW == a->OW;
-    const bool d3s2 = a->mode == 1 && a->KH == 3 && a->KW == 3 && a->SH == 2 && a->SW == 2 && a->PH == 1 && a->PW == 1 && a->Cout == 128 && !a->y_mask_bits;
-    if (!pw1 && !d3s2) return (int)hipErrorInvalidValue;
-    if ((pw1 && a->Cout % 256 != 0) || (a->y_mask_bits && (a->mode != 0 || a->act != GPV_ACT_RELU || a->relu_mask)) || (a->relu_mask_bits && a->mode != 1)) return (int)hipErrorInvalidValue;
-    if ((reinterpret_cast<uintptr_t>(a->y_mask_bits) | reinterpret_cast<uintptr_t>(a->relu_mask_bits)) & 15) return (int)hipErrorInvalidValue;
-  } else if (dry) {
-    return (int)hipErrorInvalidValue;
-  }
-  GemmK k{};
-  k.alpha = 1.0f; k.rowscale = a->rowscale; k.bias = a->bias; k.act = a->act;
-  k.cg = ConvGeom{a->IH, a->IW, a->Cs, a->Cin, a->OH, a->OW, a->KH, a->KW, a->SH, a->SW, a->PH, a->PW, a->mode == 1, 0, 0};
-  if (a->mode == 1 && a->SH == 2 && a->SW == 2 && a->OH % 2 == 0 && a->OW % 2 == 0) {
-    // stride-2 dgrad: only taps with r = (ih+PH) mod 2, s = (iw+PW) mod 2 contribute.  Order the rows by pixel parity
-    // class so that a tile is class-uniform and skips the other taps (2.25 of 9 on average for a 3x3, 1 of 4 pixels for a 1x1)
-    k.cg.cm = 1;
-    k.cg.cls_rows = a->B * (a->OH / 2) * (a->OW / 2);
-  }
-  const int T = a->KH * a->KW;
-  const int esz = a->dtype_in == GPV_F32 ? 4 : 2;
-  const int64_t vecel = 16 / esz;
-  if (a->mode == 0 || a->mode == 1) {
-    // rows = B*OH*OW output positions, N = Cout, K = T*Cin ; A = gather(x), B = w [Cout][T*Cin]
-    k.A = a->x; k.B = a->w; k.C = a->y;
-    k.M = a->B * a->OH * a->OW; k.N = a->Cout; k.K = T * a->Cin;
-    k.lda = 0; k.ldb = k.K; k.ldc = a->Cout;
-    k.res = a->res; k.ldr = a->Cout; k.mask = a->relu_mask; k.ldm = a->Cout;
-    k.vecA = al16(a->x) && (a->Cs % vecel == 0 || (a->Cs * esz) % 8 == 0) ? 1 : 0;
-    // the stem reads 16-B runs at pixel granularity (Cs = 4 bf16 = 8 B): require 16-B aligned runs
-    if ((a->Cs % vecel) != 0) k.vecA = ((a->SW * a->Cs) % vecel == 0 && (a->IW * a->Cs) % vecel == 0 && a->PW == 0) ? k.vecA : 0;
-    k.vecB = al16(a->w) && (k.K % 8 == 0) ? 1 : 0;
-    if (a->mode == 0 && a->KH == 1 && a->KW == 1 && a->SH == 2 && a->SW == 2 && a->PH == 0 && a->PW == 0 &&
-        al16(a->x) && a->Cs % vecel == 0 && (int64_t)a->B * a->IH * a->IW * a->Cs * esz < 0x7ffffff0ll * 4ll) {
-      // stride-2 pointwise projection (the downsample branches), forward: the streaming kernel reads every other pixel of every
-      // other row (conv1x1_stream.hip); anything it does not take goes down the generic gather path below
-      GemmK ks = k;
-      ks.lda = a->Cs; ks.vecA = 1;
-      const int cs = c1s_try_launch(ks, a->dtype_in, a->dtype_out, st);
-      if (cs >= 0) return cs;
-    }
-    if (a->KH == 1 && a->KW == 1 && a->SH == 1 && a->SW == 1 && a->PH == 0 && a->PW == 0 && a->IH == a->OH && a->IW == a->OW) {
-      // a 1x1 stride-1 convolution IS a GEMM over the pixel rows (row pitch Cs): no tap / pixel decoding per thread
-      // (three integer divisions per staged row -- a third of the instructions of a K = 64 tile), and the GEMM-side
-      // kernel choices apply
-      k.lda = a->Cs;
-      k.cg = ConvGeom{};
-      k.cg.SH = k.cg.SW = 1;
-      k.conv1x1 = 1;
-      {
-        // outputs far beyond the 256 MB MALL (layer1's 314 MB maps) are stored -- and their residual read -- non-temporally:
-        // 64 -> 256 without a residual 150 -> 106 us, with one 177 -> 168 us; smaller outputs are better left cacheable for
-        // the next convolution (layer3 conv3, 79 MB: 58 -> 72 us with non-temporal stores)   [tools/bench_c1.py]
-        static const int64_t nt_min = (int64_t)tune_env("GPV_NT_MIN_MB", 200) << 20;
-        k.nt_io = (int64_t)k.M * k.N * esz >= nt_min ? 1 : 0;
-      }
-      k.vecA = al16(a->x) && (a->Cs % vecel == 0) && (int64_t)k.M * a->Cs * esz < 0x7ffffff0ll ? 1 : 0;
-      if (want_bits) {
-        if (!k.vecA) return (int)hipErrorInvalidValue;
-        k.out_bits = reinterpret_cast<uint32_t*>(a->y_mask_bits);
-        k.mask_bits = reinterpret_cast<const uint32_t*>(a->relu_mask_bits);
-        if (k.mask_bits) { k.mask = a->relu_mask_bits; k.ldm = a->Cout; }      // (selects the masked instances; never dereferenced as bf16)
-        const int cs = c1s_try_launch(k, a->dtype_in, a->dtype_out, st, false, dry);
-        return cs >= 0 ? cs : (int)hipErrorInvalidValue;
-      }
-      if (k.vecA) {
-        const int cs = c1s_try_launch(k, a->dtype_in, a->dtype_out, st);
-        if (cs >= 0) return cs;
-      }
-      const int pp = pipe_try_launch(k, OP_PLAIN, a->dtype_in, a->dtype_out, 1, st);
-      if (pp >= 0) return pp;
-      if (k.M <= 8192 && !g_kernel_forced) {               // a few thousand pixels (inference at batch 1): 64x64 tiles, reduction split over the block's waves
-        const int sk = skinny_try_launch(k, 0, a->dtype_in, a->dtype_out, 1, st);
-        if (sk >= 0) return sk;
-      }
-      const int g = glds_try_launch(k, OP_PLAIN, a->dtype_in, a->dtype_out, 1, st);
-      if (g >= 0) return g;
-      return launch_dtype<OP_PLAIN, OP_PLAIN>(k, 1, a->dtype_in, a->dtype_out, st);
-    }
-    static const bool s2_split = tune_env("GPV_S2_DGRAD_SPLIT", 1) != 0;
-    if (s2_split && a->mode == 1 && k.cg.cm && a->KH == 1 && a->KW == 1 && a->PH == 0 && a->PW == 0 && a->dtype_in == GPV_BF16 &&
-        a->dtype_out == GPV_BF16 && a->Cout % 8 == 0 && al16(a->y) && (!a->res || al16(a->res)) &&
-        (!a->relu_mask || al16(a->relu_mask)) && k.vecA && k.vecB) {
-      // pointwise stride-2 backward-data: class 0 (even row, even column) through the GEMM kernels, the rest element-wise
-      GemmK k0 = k;
-      k0.M = k.cg.cls_rows;
-      int e = pipe_try_launch(k0, OP_CONV, a->dtype_in, a->dtype_out, 1, st);
-      if (e < 0) e = glds_try_launch(k0, OP_CONV, a->dtype_in, a->dtype_out, 1, st);
-      if (e < 0) e = launch_dtype<OP_CONV, OP_PLAIN>(k0, 1, a->dtype_in, a->dtype_out, st);
-      if (e) return e;
-      const int C8 = a->Cout / 8;
-      const int64_t chunks = (int64_t)a->B * a->OH * a->OW * C8;
-      hipLaunchKernelGGL(s2_dgrad_fill_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, reinterpret_cast<bf16*>(a->y),
-                         reinterpret_cast<const bf16*>(a->res), reinterpret_cast<const bf16*>(a->relu_mask), chunks, a->OW, a->OH, C8);
+// one part of a routed call
+static int launch_route(const GemmK& k, const Route& r, hipStream_t st) {
+  switch (r.family) {
+    case FAM_GEMV: return gemv_launch(k, r, st);
+    case FAM_C1S: return c1s_launch(k, r, st);
+    case FAM_C3S: return c3s_launch(k, r, st);
+    case FAM_CONV_SPLIT: return conv_split_launch(k, r, st);
+    case FAM_PIPE: return pipe_launch(k, r, st);
+    case FAM_SKINNY: return skinny_launch(k, r, st);
+    case FAM_GLDS: case FAM_HALO: return glds_launch(k, r, st);
+    case FAM_GLDS_WGRAD: case FAM_GLDS_TT: return glds_tt_launch(k, r, st);
+    case FAM_SKINNY_TT: return skinny_tt_launch(k, r, st);
+    case FAM_TILE: return tile_launch(k, r, st);
+    case FAM_S2_FILL:
+      hipLaunchKernelGGL(s2_dgrad_fill_kernel, dim3(r.gx), dim3(r.block), 0, st, reinterpret_cast<bf16*>(k.C), reinterpret_cast<const bf16*>(k.res),
+                         reinterpret_cast<const bf16*>(k.mask), (int64_t)k.M * r.ncols, k.cg.OW, k.cg.OH, r.ncols);
       GPV_CHECK_LAUNCH();
       return 0;
-    }
-    if (want_bits) {
-      // (not the pointwise form, which returned above: the stride-2 3x3 backward-data over 128 channels on the streaming kernel, or nothing)
-      if (!(a->KH == 3 && a->KW == 3 && k.vecA && k.vecB)) return (int)hipErrorInvalidValue;
-      k.mask_bits = reinterpret_cast<const uint32_t*>(a->relu_mask_bits);
-      k.mask = a->relu_mask_bits; k.ldm = a->Cout;
-      const int c3 = c3s_try_launch(k, a->dtype_in, a->dtype_out, st, dry);
-      return c3 >= 0 ? c3 : (int)hipErrorInvalidValue;
-    }
-    if (a->KH == 3 && a->KW == 3 && k.vecA && k.vecB) {
-      // 3x3 with 64 / 128 input channels over the layer1 / layer2 maps: weights resident in LDS, barrier-free streaming kernel
-      const int c3 = c3s_try_launch(k, a->dtype_in, a->dtype_out, st);
-      if (c3 >= 0) return c3;
-    }
-    if (k.vecA && k.vecB) {
-      if (a->mode == 0 && a->workspace) {                  // few output pixels, long reduction (inference at batch 1): split + second pass
-        GemmK ks = k;
-        ks.ws_base = a->workspace; ks.ws_bytes = a->workspace_bytes;
-        const int cs = conv_split_try_launch(ks, a->dtype_in, a->dtype_out, st);
-        if (cs >= 0) return cs;
-      }
-      const int pp = pipe_try_launch(k, OP_CONV, a->dtype_in, a->dtype_out, 1, st);
-      if (pp >= 0) return pp;
-      const int g = glds_try_launch(k, OP_CONV, a->dtype_in, a->dtype_out, 1, st);
-      if (g >= 0) return g;
-    }
-    return launch_dtype<OP_CONV, OP_PLAIN>(k, 1, a->dtype_in, a->dtype_out, st);
-  }
-  if (a->mode == 2) {
-    // dw[Cout][T*Cin] += dy^T x_gather : M = Cout, N = T*Cin, K = B*OH*OW
-    if (a->dtype_out != GPV_F32) return (int)hipErrorInvalidValue;
-    if (a->Cin % 64 != 0) return (int)hipErrorInvalidValue;
-    k.A = a->w /* dy */; k.B = a->x; k.C = a->y /* dw */;
-    k.M = a->Cout; k.N = T * a->Cin; k.K = a->B * a->OH * a->OW;
-    k.lda = a->Cout; k.ldb = 0; k.ldc = k.N;
-    k.accumulate = 1;
-    int split = a->split_k;
-    if (split < 1) {
-      const int kt = (k.K + BK - 1) / BK;
-      int64_t want;
-      if (a->workspace && a->Cin % 128 == 0 && k.M >= 128) {
-        // two-pass reduction (no atomics): ~2 blocks of 128x128 per CU is the measured optimum on the layer2-4 shapes
-        // (tools/bench_split_conv.py: 64..96 / 64 / 32 / 16 / 8 / 4 splits for 4 / 9 / 16 / 36 / 64 / 144 tiles)
-        const int64_t t128 = (int64_t)((k.M + 127) / 128) * (k.N / 128);
-        want = (544 + t128 / 2) / t128;
-        if (want > 288) want = 288;
-        while (want > 1 && want * (int64_t)k.M * k.N * 4 > a->workspace_bytes) --want;
-      } else {
-        const int64_t tiles = (int64_t)((k.M + 63) / 64) * ((k.N + 63) / 64);
-        want = 1536 / (tiles > 0 ? tiles : 1);
-      }
-      if (want > kt / 8) want = kt / 8;
-      split = want < 1 ? 1 : (int)want;
-    }
-    k.split_k = split;
-    if (split <= 1) { k.accumulate = 0; k.res = a->y; k.ldr = k.ldc; }
-    k.ws_base = a->workspace; k.ws_bytes = a->workspace ? a->workspace_bytes : 0;
-    k.vecA = al16(a->w) && (a->Cout % vecel == 0) ? 1 : 0;
-    k.vecB = al16(a->x) && (a->Cs % vecel == 0) ? 1 : 0;
-    // CONVT needs every N tile inside one tap: BN divides Cin (64 always does here; 128 when Cin % 128 == 0)
-    {   // direct-to-LDS kernel (gemm_glds_tt.hip): 128-multiples of Cout / Cin with a workspace split reduction
-      const int gw = glds_wgrad_try_launch(k, a->dtype_in, a->dtype_out, st);
-      if (gw >= 0) return gw;
-    }
-    static const int wforce = tune_env("GPV_FORCE_WGRAD_TILE", 0);   // tuning only
-    if (a->dtype_in == GPV_BF16) {
-      const bool can128 = (a->Cin % 128 == 0) && k.M >= 128;
-      int cfg;   // 0: 128x128, 1: 128x64, 2: 64x64
-      if (wforce) cfg = wforce - 1;
-      else if (can128 && (int64_t)((k.M + 127) / 128) * (k.N / 128) * split >= 256) cfg = 0;
-      else if (k.M >= 128 && (int64_t)((k.M + 127) / 128) * (k.N / 64) * split >= 384) cfg = 1;
-      else cfg = 2;
-      if (cfg == 0 && can128) return launch_cfg<bf16, float, OP_TRANS, OP_CONV, 128, 128>(k, 1, st);
-      if (cfg <= 1 && k.M >= 128) return launch_cfg<bf16, float, OP_TRANS, OP_CONV, 128, 64>(k, 1, st);
-      return launch_cfg<bf16, float, OP_TRANS, OP_CONV, 64, 64>(k, 1, st);
-    }
-    return launch_cfg<float, float, OP_TRANS, OP_CONV, 64, 64>(k, 1, st);
   }
   return (int)hipErrorInvalidValue;
 }
 
-extern "C" int gpv_conv2d(const gpv_conv_args* a, void* stream) { return conv2d_impl(a, reinterpret_cast<hipStream_t>(stream), false); }
+static int launch_routed(Routed& rt, hipStream_t st) {
+  if (rt.err) return rt.err;
+  for (int i = 0; i < rt.nparts; ++i) {
+    rt.k[i].seed_dev = gpvk::g_seed_dev;
+    const int e = launch_route(rt.k[i], rt.r[i], st);
+    if (e) return e;
+  }
+  return 0;
+}
 
-extern "C" int gpv_conv2d_mask_bits_ok(const gpv_conv_args* a) { return conv2d_impl(a, nullptr, true) == 0 ? 1 : 0; }
+extern "C" int gpv_gemm(const gpv_gemm_args* a, void* stream) {
+  Routed rt;
+  route_gemm(a, g_knobs, &rt);
+  return launch_routed(rt, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int gpv_conv2d(const gpv_conv_args* a, void* stream) {
+  Routed rt;
+  route_conv2d(a, g_knobs, &rt);
+  return launch_routed(rt, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int gpv_conv2d_mask_bits_ok(const gpv_conv_args* a) {
+  if (!a || (!a->y_mask_bits && !a->relu_mask_bits)) return 0;
+  Routed rt;
+  route_conv2d(a, g_knobs, &rt);
+  return rt.err == 0 ? 1 : 0;
+}
+
+namespace gpvk { int attn_bwd1_mode(int set); long attn_bwd1_launches(long set); }   // attention.hip
+
+// option number -> Knobs field (a mode) or launch counter.  Returns the previous value, -1 for an unknown option.
+extern "C" int gpv_set_option(int option, int value) {
+  static const struct { int option; int Knobs::* mode; long Knobs::* count; } table[] = {
+      {GPV_OPT_GLDS, &Knobs::glds, nullptr},           {GPV_OPT_GLDS_LAUNCHES, nullptr, &Knobs::n_glds},
+      {GPV_OPT_SKINNY, &Knobs::skinny, nullptr},       {GPV_OPT_GLDS_WGRAD, &Knobs::wgrad, nullptr},
+      {GPV_OPT_PIPE, &Knobs::pipe, nullptr},           {GPV_OPT_PIPE_LAUNCHES, nullptr, &Knobs::n_pipe},
+      {GPV_OPT_C1S, &Knobs::c1s, nullptr},             {GPV_OPT_C1S_LAUNCHES, nullptr, &Knobs::n_c1s},
+      {GPV_OPT_C3S, &Knobs::c3s, nullptr},             {GPV_OPT_C3S_LAUNCHES, nullptr, &Knobs::n_c3s},
+      {GPV_OPT_GEMV, &Knobs::gemv, nullptr},           {GPV_OPT_GEMV_LAUNCHES, nullptr, &Knobs::n_gemv},
+      {GPV_OPT_WG8, &Knobs::wg8, nullptr},             {GPV_OPT_WG8_LAUNCHES, nullptr, &Knobs::n_wg8},
+      {GPV_OPT_W8L, &Knobs::w8l, nullptr},             {GPV_OPT_WG8H, &Knobs::wg8h, nullptr},
+      {GPV_OPT_PIPE_SMALL, &Knobs::pipe_small, nullptr},
+      {GPV_OPT_C3_HALO, &Knobs::halo, nullptr},        {GPV_OPT_C3_HALO_LAUNCHES, nullptr, &Knobs::n_halo},
+  };
+  if (option == GPV_OPT_ATTN_BWD1) return gpvk::attn_bwd1_mode(value);
+  if (option == GPV_OPT_ATTN_BWD1_LAUNCHES) return (int)gpvk::attn_bwd1_launches(value);
+  for (const auto& t : table) {
+    if (t.option != option) continue;
+    if (t.mode) { const int prev = g_knobs.*t.mode; g_knobs.*t.mode = value; return prev; }
+    const long prev = g_knobs.*t.count;
+    if (value >= 0 || option != GPV_OPT_PIPE_LAUNCHES) g_knobs.*t.count = value;      // (the pipe counter has always ignored a negative value)
+    return (int)prev;
+  }
+  return -1;
+}

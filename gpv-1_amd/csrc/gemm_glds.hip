@@ -30,10 +30,6 @@
 namespace gpvk {
 namespace {
 
-constexpr int GBK = 64;       // k-tile in elements
-constexpr int ROWB = 128;     // bytes per staged operand row
-constexpr int GBM = 256;
-long g_glds_launches = 0;     // gpv_set_option(GPV_OPT_GLDS_LAUNCHES, .)
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -428,8 +424,6 @@ __global__ __launch_bounds__(BM == 256 ? 512 : 256) void glds_kernel(GemmK p) {
 //     out-of-range DMA offset did per tap;
 //   * delivered bytes per 64 channels: (BM + 96) x 128 + 9 x 16 KB instead of 9 x (BM x 128 + 16 KB).
 // Register epilogue, XCD-aware tile order, loaders and fragment layout are glds_body's.  W <= 47, Cin % 64 == 0, N % 128 == 0.
-int g_halo_mode = tune_env("GPV_C3_HALO", 1);       // gpv_set_option(GPV_OPT_C3_HALO, .): 0 never, 1 the 160-row tiles (where it wins), 2 the 96-row tiles as well
-long g_halo_launches = 0;
 
 template <int BM>
 __global__ __launch_bounds__(256) void glds_halo_kernel(GemmK p) {
@@ -604,11 +598,10 @@ __global__ __launch_bounds__(256) void glds_halo_kernel(GemmK p) {
 }
 
 template <int BM>
-int launch_halo(const GemmK& k, hipStream_t st) {
+int launch_halo(const GemmK& k, const Route& r, hipStream_t st) {
   constexpr size_t lds = (size_t)(BM + 96) * ROWB + (size_t)2 * 128 * ROWB;
   GemmK p = k;
-  const int tilesM = (p.M + BM - 1) / BM;
-  p.tilesN = p.N / 128;
+  p.tilesN = r.tilesN;
   auto fn = glds_halo_kernel<BM>;
   static bool attr_done = false;
   if (!attr_done) {
@@ -616,19 +609,11 @@ int launch_halo(const GemmK& k, hipStream_t st) {
     if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
     attr_done = true;
   }
-  ++g_halo_launches;
-  ++g_glds_launches;                  // (a launch of the two-per-CU tile family: tests that ask whether a shape took it count these too)
-  hipLaunchKernelGGL(fn, dim3(tilesM * p.tilesN), dim3(256), lds, st, p);
+  ++g_knobs.n_halo;
+  ++g_knobs.n_glds;                  // (a launch of the two-per-CU tile family: tests that ask whether a shape took it count these too)
+  hipLaunchKernelGGL(fn, dim3(r.gx), dim3(r.block), lds, st, p);
   GPV_CHECK_LAUNCH();
   return 0;
-}
-
-inline bool halo_ok(const GemmK& k, int dtype_out, int batch) {
-  const ConvGeom& g = k.cg;
-  return g_halo_mode != 0 && dtype_out == GPV_BF16 && batch == 1 && g.KH == 3 && g.KW == 3 && g.SH == 1 && g.SW == 1 && g.PH == 1 && g.PW == 1 &&
-         !g.cm && g.OH == g.IH && g.OW == g.IW && g.IW <= 47 && g.Cin % GBK == 0 && k.N % 128 == 0 && k.K == 9 * g.Cin &&
-         k.M % (g.IH * g.IW) == 0 && k.ldc % 8 == 0 && al16(k.C) && (!k.res || (k.ldr % 8 == 0 && al16(k.res))) &&
-         (!k.mask || (k.ldm % 8 == 0 && al16(k.mask))) && (!k.bias || al16(k.bias)) && !k.dthresh && k.act != GPV_ACT_GELU;
 }
 
 // 1x1 stride-1 convolutions are plain GEMMs over the NHWC rows; their own kernel name keeps them attributable to the
@@ -640,14 +625,13 @@ __global__ __launch_bounds__(BM == 256 ? 512 : 256) void glds_conv1x1_kernel(Gem
 }
 
 template <int AMODE, int BM, int BN, typename TOut>
-int launch_glds(const GemmK& k, int batch, hipStream_t st) {
+int launch_glds(const GemmK& k, const Route& r, hipStream_t st) {
   constexpr size_t stage = (size_t)2 * (BM + BN) * ROWB;
   constexpr size_t epi = (size_t)(BM / 2) * (BN + 4) * 4;
   constexpr size_t lds = stage > epi ? stage : epi;
   GemmK p = k;
-  const int tilesM = (p.M + BM - 1) / BM;
-  p.tilesN = (p.N + BN - 1) / BN;
-  const bool c11 = AMODE == OP_PLAIN && p.conv1x1;
+  p.tilesN = r.tilesN;
+  const bool c11 = r.c11;
   auto fn = c11 ? glds_conv1x1_kernel<BM, BN, TOut> : glds_kernel<AMODE, BM, BN, TOut>;
   static bool attr_done[2] = {false, false};
   if (!attr_done[c11]) {
@@ -655,172 +639,32 @@ int launch_glds(const GemmK& k, int batch, hipStream_t st) {
     if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }      // (leave no stale error behind for the next launch check)
     attr_done[c11] = true;
   }
-  static const int depi = tune_env("GPV_GLDS_DEPI", 1);
-  p.depi = depi;
-  dim3 grid(tilesM * p.tilesN, 1, batch);
-  ++g_glds_launches;
-  hipLaunchKernelGGL(fn, grid, dim3(BM == 256 ? 512 : 256), lds, st, p);
+  p.depi = r.depi;
+  ++g_knobs.n_glds;
+  hipLaunchKernelGGL(fn, dim3(r.gx, r.gy, r.gz), dim3(BM == 256 ? 512 : 256), lds, st, p);
   GPV_CHECK_LAUNCH();
   return 0;
 }
 
 template <int AMODE, int BM, int BN>
-int launch_glds_out(const GemmK& k, int dtype_out, int batch, hipStream_t st) {
-  if (dtype_out == GPV_BF16) return launch_glds<AMODE, BM, BN, bf16>(k, batch, st);
-  return launch_glds<AMODE, BM, BN, float>(k, batch, st);
+int launch_glds_out(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.dt_out == GPV_BF16) return launch_glds<AMODE, BM, BN, bf16>(k, r, st);
+  return launch_glds<AMODE, BM, BN, float>(k, r, st);
+}
+
+template <int AMODE>
+int launch_glds_tile(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.bm == 160) return launch_glds_out<AMODE, 160, 128>(k, r, st);
+  if (r.bm == 96) return launch_glds_out<AMODE, 96, 128>(k, r, st);
+  if (r.bm == 128) return launch_glds_out<AMODE, 128, 128>(k, r, st);
+  return r.bn == 256 ? launch_glds_out<AMODE, 256, 256>(k, r, st) : launch_glds_out<AMODE, 256, 128>(k, r, st);
 }
 
 }  // namespace
-int g_kernel_forced = 0;      // bit 0: GPV_OPT_GLDS >= 2, bit 1: GPV_OPT_PIPE >= 100 -- a kernel family is being forced (tests / tuning): the small-problem side paths step aside
-int g_two_per_cu = tune_env("GPV_TWO_PER_CU", 1);
-int g_bm96_fill = tune_env("GPV_BM96", 1);       // 96-row tiles for <= 1024-row GEMMs (gemm_common.h two_per_cu_bm)
-namespace {
-int g_glds_mode = tune_env("GPV_GLDS", 1);   // gpv_set_option(GPV_OPT_GLDS, .)
 
-}  // namespace
-
-int glds_try_launch(const GemmK& k, int amode, int dtype_in, int dtype_out, int batch, hipStream_t st) {
-  const int mode = g_glds_mode;     // 0 = never, 1 (default) = where it is expected to win, 2 / 3 = the 8-wave / 4-wave variant wherever legal
-  if (mode == 0 || dtype_in != GPV_BF16) return -1;
-  if (k.accumulate || k.split_k > 1) return -1;
-  if (k.K % GBK != 0 || k.K < GBK || k.N <= 64) return -1;
-  if (!al16(k.A) || !al16(k.B) || k.ldb % 8 != 0 || (batch > 1 && (k.sA % 8 != 0 || k.sB % 8 != 0))) return -1;
-  // 32-bit byte offsets into each operand (one buffer descriptor per operand and batch element)
-  const int64_t lim = 0x7ffffff0ll / 2;
-  if ((int64_t)k.N * k.ldb >= lim) return -1;
-  if (amode == OP_CONV) {
-    if ((int64_t)k.cg.IH * k.cg.IW * k.cg.Cs * ((int64_t)k.M / ((int64_t)k.cg.OH * k.cg.OW) + 1) >= lim) return -1;
-    if (k.cg.Cin % GBK != 0 || k.cg.Cs % 8 != 0) return -1;
-  } else if (amode == OP_PLAIN) {
-    if (k.lda % 8 != 0 || (int64_t)k.M * k.lda >= lim) return -1;
-  } else {
-    return -1;
-  }
-  // one-tile-per-CU launches (layer3 / layer4 at B = 32: 240 tiles of 160 x 256) serialise load ramp, main loop and store burst:
-  // ~16 us of fixed cost on a 33-57 us kernel (tools/bench_ktile.py).  Half-width tiles at two blocks per CU (160 x 128: 480
-  // tiles, 96 x 128 for the 9600-row maps) let one block's epilogue run under the other's main loop.
-  if (glds_two_per_cu(k, batch) && mode != 2 && mode != 3) {
-    const int bm2 = two_per_cu_bm(k, batch);
-    if (amode == OP_CONV && halo_ok(k, dtype_out, batch)) {
-      if (bm2 == 160) return launch_halo<160>(k, st);
-      if (bm2 == 96 && g_halo_mode >= 2) return launch_halo<96>(k, st);     // 96-row tiles (layer4): forward 57.2 against 55.0 us, backward-data equal (tools/bench_c3_halo.py) -- tests only
-    }
-    if (bm2 == 160) return amode == OP_CONV ? launch_glds_out<OP_CONV, 160, 128>(k, dtype_out, batch, st) : launch_glds_out<OP_PLAIN, 160, 128>(k, dtype_out, batch, st);
-    if (bm2 == 96) return amode == OP_CONV ? launch_glds_out<OP_CONV, 96, 128>(k, dtype_out, batch, st) : launch_glds_out<OP_PLAIN, 96, 128>(k, dtype_out, batch, st);
-  }
-  const int bn = k.N > 128 ? 256 : 128;
-  bool small_tiles = mode == 3;
-  if (mode == 1) {
-    // Measured per shape on the ResNet-50 / transformer launches at B=32 (tools/bench_conv.py, bench_dgrad.py,
-    // bench_gemm_sq.py with GPV_GLDS=0/2/3).  At 1-2 256-row tiles per CU the 8-wave kernel loses to kernels with 2-3
-    // co-resident blocks (epilogues overlapped with other blocks' main loops, finer tail); it keeps the launches that fill the
-    // chip several times over.  The 4-wave 128x128 variant wins wherever the reduction is long enough to amortise its
-    // prologue/epilogue: every K >= 1024 conv / GEMM (layer3/4 3x3 fwd 94->82 / 150->76 us, their stride-2 dgrads
-    // 194->139 / 161->101 us) and the K = 512 forward 1x1s; ReLU-mask (dgrad) epilogues need K >= 1024.
-    const int64_t tiles = (int64_t)((k.M + GBM - 1) / GBM) * ((k.N + bn - 1) / bn) * batch;
-    const bool huge = tiles >= 1024 && k.K >= 512 && !(amode == OP_CONV && k.cg.cm);   // parity classes: too unbalanced for 1 block/CU
-    small_tiles = !huge && (k.K >= 1024 || (k.K >= 512 && !k.mask));
-    if (!huge && !small_tiles) return -1;
-  }
-  if (small_tiles)   // 4-wave 128x128 variant, two blocks per CU
-    return amode == OP_CONV ? launch_glds_out<OP_CONV, 128, 128>(k, dtype_out, batch, st) : launch_glds_out<OP_PLAIN, 128, 128>(k, dtype_out, batch, st);
-  if (amode == OP_CONV) return bn == 256 ? launch_glds_out<OP_CONV, 256, 256>(k, dtype_out, batch, st) : launch_glds_out<OP_CONV, 256, 128>(k, dtype_out, batch, st);
-  return bn == 256 ? launch_glds_out<OP_PLAIN, 256, 256>(k, dtype_out, batch, st) : launch_glds_out<OP_PLAIN, 256, 128>(k, dtype_out, batch, st);
+int glds_launch(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.family == FAM_HALO) return r.bm == 160 ? launch_halo<160>(k, r, st) : launch_halo<96>(k, r, st);
+  return r.amode == OP_CONV ? launch_glds_tile<OP_CONV>(k, r, st) : launch_glds_tile<OP_PLAIN>(k, r, st);
 }
 
 }  // namespace gpvk
-
-namespace gpvk { int attn_bwd1_mode(int set); long attn_bwd1_launches(long set); }   // attention.hip
-
-extern "C" int gpv_set_option(int option, int value) {
-  if (option == GPV_OPT_C1S_LAUNCHES) {
-    const long prev = gpvk::g_c1s_launches;
-    gpvk::g_c1s_launches = value;
-    return (int)prev;
-  }
-  if (option == GPV_OPT_ATTN_BWD1) return gpvk::attn_bwd1_mode(value);
-  if (option == GPV_OPT_ATTN_BWD1_LAUNCHES) return (int)gpvk::attn_bwd1_launches(value);
-  if (option == GPV_OPT_GLDS) {
-    const int prev = gpvk::g_glds_mode;
-    gpvk::g_glds_mode = value;
-    gpvk::g_kernel_forced = (gpvk::g_kernel_forced & ~1) | (value >= 2 ? 1 : 0);
-    return prev;
-  }
-  if (option == GPV_OPT_SKINNY) {
-    const int prev = gpvk::g_skinny_mode;
-    gpvk::g_skinny_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_GEMV) {
-    const int prev = gpvk::g_gemv_mode;
-    gpvk::g_gemv_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_GEMV_LAUNCHES) {
-    const long prev = gpvk::g_gemv_launches;
-    gpvk::g_gemv_launches = value;
-    return (int)prev;
-  }
-  if (option == GPV_OPT_WG8) {
-    const int prev = gpvk::g_wg8_mode;
-    gpvk::g_wg8_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_PIPE_SMALL) return gpvk::pipe_set_small(value);
-  if (option == GPV_OPT_WG8H) {
-    const int prev = gpvk::g_wg8h_mode;
-    gpvk::g_wg8h_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_W8L) {
-    const int prev = gpvk::g_w8l_mode;
-    gpvk::g_w8l_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_WG8_LAUNCHES) {
-    const long prev = gpvk::g_wg8_launches;
-    gpvk::g_wg8_launches = value;
-    return (int)prev;
-  }
-  if (option == GPV_OPT_GLDS_WGRAD) {
-    const int prev = gpvk::g_wgrad_mode;
-    gpvk::g_wgrad_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_C1S) {
-    const int prev = gpvk::g_c1s_mode;
-    gpvk::g_c1s_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_C3S) {
-    const int prev = gpvk::g_c3s_mode;
-    gpvk::g_c3s_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_C3S_LAUNCHES) {
-    const long prev = gpvk::g_c3s_launches;
-    gpvk::g_c3s_launches = value;
-    return (int)prev;
-  }
-  if (option == GPV_OPT_PIPE) {
-    gpvk::g_kernel_forced = (gpvk::g_kernel_forced & ~2) | (value >= 100 ? 2 : 0);
-    return gpvk::pipe_set_mode(value);
-  }
-  if (option == GPV_OPT_PIPE_LAUNCHES) return (int)gpvk::pipe_launches(value);
-  if (option == GPV_OPT_C3_HALO) {
-    const int prev = gpvk::g_halo_mode;
-    gpvk::g_halo_mode = value;
-    return prev;
-  }
-  if (option == GPV_OPT_C3_HALO_LAUNCHES) {
-    const long prev = gpvk::g_halo_launches;
-    gpvk::g_halo_launches = value;
-    return (int)prev;
-  }
-  if (option == GPV_OPT_GLDS_LAUNCHES) {
-    const long prev = gpvk::g_glds_launches;
-    gpvk::g_glds_launches = value;
-    return (int)prev;
-  }
-  return -1;
-}

@@ -23,10 +23,6 @@
 namespace gpvk {
 namespace {
 
-constexpr int TBM = 128, TBN = 128, TBK = 64;
-constexpr int ROWBYTES = 256;                      // one pixel row of a 128-column operand tile
-constexpr int OP_BYTES = TBK * ROWBYTES;           // 16 KB
-constexpr int TSTAGE = 2 * OP_BYTES;
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -929,75 +925,30 @@ __global__ __launch_bounds__(256) void wgrad_group_reduce_kernel(WgRedK g) {
   *dst = c;
 }
 
-// shared launch tail: split sizing, workspace slabs, kernel, reduction
+// shared launch tail: workspace slabs, kernel, reduction
 template <typename F>
-int launch_tt(F fn, const GemmK& k, bool& attr_done, hipStream_t st) {
+int launch_tt(F fn, const GemmK& k, const Route& r, bool& attr_done, hipStream_t st) {
   GemmK p = k;
-  const int kt_total = (p.K + TBK - 1) / TBK;
-  // two 64 KB blocks per CU = 512 resident blocks: size the split so that (tiles x splits) fills them once -- the 544 the
-  // register-staged kernel (three blocks per CU) is tuned for would leave a second, almost empty round
-  static const int target = tune_env("GPV_WGRAD_TARGET", 512);
-  const int tiles = (p.M / TBM) * (p.N / TBN);
-  int split = target / tiles;
-  if (split > kt_total / 4) split = kt_total / 4;
-  if (split < 2) return -1;
-  while (split > 2 && (int64_t)split * p.M * p.N * 4 > k.ws_bytes) --split;
-  p.kt_per_split = (kt_total + split - 1) / split;
-  split = (kt_total + p.kt_per_split - 1) / p.kt_per_split;
-  if (split < 2 || (int64_t)split * p.M * p.N * 4 > k.ws_bytes) return -1;
+  p.kt_per_split = r.kt_per_split;
   p.ws = reinterpret_cast<float*>(k.ws_base);
-  p.tilesN = p.N / TBN;
-  constexpr int lds = 2 * TSTAGE;                    // 64 KB (the fp32 epilogue image needs 33 KB)
+  p.tilesN = r.tilesN;
   if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
     if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }      // (leave no stale error behind for the next launch check)
     attr_done = true;
   }
-  dim3 grid((p.M / TBM) * p.tilesN, split, 1);
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, p);
+  hipLaunchKernelGGL(fn, dim3(r.gx, r.gy, r.gz), dim3(r.block), (size_t)r.lds, st, p);
   GPV_CHECK_LAUNCH();
-  return launch_splitk_reduce(p.ws, split, p.M, p.N, reinterpret_cast<float*>(p.C), p.ldc, st);
+  return launch_splitk_reduce(p.ws, r.split, p.M, p.N, reinterpret_cast<float*>(p.C), p.ldc, st);
 }
 
 }  // namespace
 
-int g_wgrad_mode = tune_env("GPV_GLDS_WGRAD", 1);   // gpv_set_option(GPV_OPT_GLDS_WGRAD, .)
-int g_wg8_mode = tune_env("GPV_WG8", 1);            // gpv_set_option(GPV_OPT_WG8, .): eight-phase 256 x 256 weight-gradient kernel
-long g_wg8_launches = 0;
-int g_wg8h_mode = tune_env("GPV_WG8H", 1);          // gpv_set_option(GPV_OPT_WG8H, .): the 128 x 256 | 256 x 128 eight-phase tiles for the problems with a 128-wide side (layer2)
-int g_w8l_mode = tune_env("GPV_W8L", 0);            // gpv_set_option(GPV_OPT_W8L, .): the same kernel on the linear weight-gradient groups -- OFF by default: alone on the chip the step's 123
-                                                    // linear gradients take 810 instead of 885 us with it, inside the step nothing (16.63 / 16.60 ms off, 16.66 / 16.77 on, same box): its
-                                                    // 128 KB blocks take whole CUs from the backward chain they run beside
-
-// conv weight gradient (k as prepared by gpv_conv2d mode 2: A = dy [K][M], B = x NHWC, C = dw [M][N] fp32, split chosen).
-// returns 0 = launched (partial products + reduction), -1 = not applicable, > 0 = hipError_t
-int glds_wgrad_try_launch(const GemmK& k, int dtype_in, int dtype_out, hipStream_t st) {
-  if (g_wgrad_mode == 0 || dtype_in != GPV_BF16 || dtype_out != GPV_F32) return -1;
-  const ConvGeom& g = k.cg;
-  if (k.M % TBM != 0 || g.Cin % TBN != 0 || k.N % TBN != 0) return -1;
-  if (g.Cs % 8 != 0 || k.lda % 8 != 0 || !al16(k.A) || !al16(k.B)) return -1;
-  if (TBK / g.OW + 2 > g.OH || (int64_t)g.IH * g.IW * g.Cs * (k.K / (g.OH * g.OW)) >= (1ll << 30) ||
-      (int64_t)k.K * k.lda >= (1ll << 30)) return -1;
-  if (!k.accumulate || k.ws_base == nullptr || !al16(k.C) || k.ldc % 4 != 0) return -1;
-  static bool attr_done = false;
-  return launch_tt(glds_wgrad_kernel, k, attr_done, st);
-}
-
-// linear weight gradient dW[M][N] += dY^T X (A = dy [K][M], B = x [K][N], both reduction-major), optional a_rowsum (bias
-// gradient).  Same return convention.
-int glds_tt_try_launch(const GemmK& k, int dtype_in, int dtype_out, int batch, hipStream_t st) {
-  if (g_wgrad_mode == 0 || dtype_in != GPV_BF16 || dtype_out != GPV_F32 || batch != 1) return -1;
-  if (k.M % TBM != 0 || k.N % TBN != 0 || k.K < 8 * TBK) return -1;
-  if ((int64_t)k.K * k.lda >= (1ll << 30) || (int64_t)k.K * k.ldb >= (1ll << 30)) return -1;
-  // measured on every linear weight-gradient shape of the step (tools/bench_step_gemms.py, GPV_GLDS_WGRAD=0 vs 2): it wins
-  // once there is enough work to fill the chip -- 768x3072 / 3072x768 over 3200 rows 52 -> 35 us, 1536x768 36 -> 26 us,
-  // 2048x256 over 9600 rows 33 -> 27 us -- and loses on the 4..36-tile gradients of short reductions (skinny_tt's territory)
-  if (g_wgrad_mode == 1 && (int64_t)(k.M / TBM) * (k.N / TBN) * ((k.K + TBK - 1) / TBK) < 3000) return -1;
-  if (k.lda % 8 != 0 || k.ldb % 8 != 0 || !al16(k.A) || !al16(k.B)) return -1;
-  if (!k.accumulate || k.ws_base == nullptr || !al16(k.C) || k.ldc % 4 != 0) return -1;
-  if (k.res || k.mask || k.bias || k.act || k.dthresh) return -1;
-  static bool attr_done = false;
-  return launch_tt(glds_tt_kernel, k, attr_done, st);
+// FAM_GLDS_WGRAD: conv weight gradient; FAM_GLDS_TT: linear weight gradient (+ a_rowsum)
+int glds_tt_launch(const GemmK& k, const Route& r, hipStream_t st) {
+  static bool attr_done[2] = {false, false};
+  if (r.family == FAM_GLDS_WGRAD) return launch_tt(glds_wgrad_kernel, k, r, attr_done[0], st);
+  return launch_tt(glds_tt_kernel, k, r, attr_done[1], st);
 }
 
 }  // namespace gpvk
@@ -1082,11 +1033,11 @@ extern "C" int gpv_conv_wgrad_group(const gpv_conv_wgrad_problem* probs, int n, 
   // a 128-wide side: Cout or Cin an odd multiple of 128 (or a 256-multiple problem the 256 x 256 launch did not take)
   auto eligible8h = [&](const gpv_conv_wgrad_problem& q) {
     const int64_t K64 = (int64_t)q.B * q.OH * q.OW;
-    return g_wg8h_mode != 0 && q.Cout % 128 == 0 && q.Cin % 128 == 0 && q.Cs % 8 == 0 && al16(q.dy) && al16(q.x) && al16(q.dw) &&
+    return g_knobs.wg8h != 0 && q.Cout % 128 == 0 && q.Cin % 128 == 0 && q.Cs % 8 == 0 && al16(q.dy) && al16(q.x) && al16(q.dw) &&
            TBK / q.OW + 2 <= q.OH && (int64_t)q.IH * q.IW * q.Cs * q.B < (1ll << 30) && K64 * q.Cout < (1ll << 30) && K64 >= 8 * TBK;
   };
-  bool use8 = g_wg8_mode != 0;
-  if (use8 && g_wg8_mode == 1) {
+  bool use8 = g_knobs.wg8 != 0;
+  if (use8 && g_knobs.wg8 == 1) {
     int64_t u8 = 0;
     for (int i = 0; i < n; ++i) {
       const gpv_conv_wgrad_problem& q = probs[i];
@@ -1100,7 +1051,7 @@ extern "C" int gpv_conv_wgrad_group(const gpv_conv_wgrad_problem* probs, int n, 
   // makespan is rounds x (unit length + ramp) -- measured on layer2's call (B = 32): 60 / 75 / 100 / 120 / 150 / 200 / 300 k-tiles
   // per unit = 7 / 6 / 4 / 4 / 3 / 2 / 2 rounds -> 676 / 698 / 617 / 700 / 644 / 590 / 807 us.  Pick the length that minimises it.
   int target_kt8h = forced_kt8h >= 8 ? forced_kt8h : 150;
-  if (forced_kt8h < 8 && g_wg8h_mode != 0) {
+  if (forced_kt8h < 8 && g_knobs.wg8h != 0) {
     int64_t best = -1;
     for (int kt = 64; kt <= 640; kt += 4) {
       int64_t u = 0;
@@ -1133,13 +1084,13 @@ extern "C" int gpv_conv_wgrad_group(const gpv_conv_wgrad_problem* probs, int n, 
       g8.ws = reinterpret_cast<float*>(workspace);
       hipLaunchKernelGGL(wg8_group_kernel, dim3(units8), dim3(512), W8_LDS, st, g8);
       GPV_CHECK_LAUNCH();
-      ++g_wg8_launches;
+      ++g_knobs.n_wg8;
     }
     if (gh.n > 0) {
       gh.ws = reinterpret_cast<float*>(workspace);
       hipLaunchKernelGGL(wg8h_group_kernel, dim3(unitsh), dim3(512), W8H_LDS, st, gh);
       GPV_CHECK_LAUNCH();
-      ++g_wg8_launches;
+      ++g_knobs.n_wg8;
     }
     if (g.n > 0) {
       g.ws = reinterpret_cast<float*>(workspace);
@@ -1279,7 +1230,7 @@ extern "C" int gpv_gemm_tt_group_ws(const gpv_tt_problem* problems, int n, void*
     g.ws = reinterpret_cast<float*>(workspace);
     hipLaunchKernelGGL(wg8_tt_group_kernel, dim3(8 * Q), dim3(512), W8_LDS, st, g);
     GPV_CHECK_LAUNCH();
-    ++g_wg8_launches;
+    ++g_knobs.n_wg8;
     if (rk.n > 0) {
       hipLaunchKernelGGL(wgrad_group_reduce_kernel, dim3(rblocks), dim3(256), 0, st, rk);
       GPV_CHECK_LAUNCH();
@@ -1289,7 +1240,7 @@ extern "C" int gpv_gemm_tt_group_ws(const gpv_tt_problem* problems, int n, void*
   };
   for (int i = 0; i < n; ++i) {
     const gpv_tt_problem& q = problems[i];
-    const bool big = g_w8l_mode != 0 && q.A && q.B && q.C && q.M > 0 && q.N > 0 && q.M % 256 == 0 && q.N % 256 == 0 && q.K >= 2 * TBK && (int64_t)q.M * q.N < (1ll << 30) &&
+    const bool big = g_knobs.w8l != 0 && q.A && q.B && q.C && q.M > 0 && q.N > 0 && q.M % 256 == 0 && q.N % 256 == 0 && q.K >= 2 * TBK && (int64_t)q.M * q.N < (1ll << 30) &&
                      q.lda % 8 == 0 && q.ldb % 8 == 0 && q.ldc % 4 == 0 && al16(q.A) && al16(q.B) && al16(q.C) &&
                      (int64_t)q.K * q.lda < (1ll << 30) && (int64_t)q.K * q.ldb < (1ll << 30);
     if (!big) {

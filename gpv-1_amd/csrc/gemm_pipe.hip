@@ -28,10 +28,7 @@
 namespace gpvk {
 namespace {
 
-constexpr int GBK = 64;
-constexpr int ROWB = 128;
-constexpr int NW = 8, NT = 512;
-long g_pipe_launches = 0;
+constexpr int NW = 8, NT = PIPE_THREADS;
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
@@ -424,14 +421,14 @@ __global__ __launch_bounds__(NT) void pipe_conv1x1_kernel(GemmK p) {
 }
 
 template <int AMODE, int BM, int BN, int WM, int NS>
-int launch_pipe(const GemmK& k, int batch, hipStream_t st) {
+int launch_pipe(const GemmK& k, const Route& r, hipStream_t st) {
   constexpr size_t stages = (size_t)NS * (BM + BN) * ROWB;
   constexpr size_t lds = stages + (AMODE == OP_CONV ? (size_t)BM * 4 : 0);
   static_assert(lds <= 160 * 1024, "LDS budget");
   GemmK p = k;
-  const int tilesM = (p.M + BM - 1) / BM;
-  p.tilesN = (p.N + BN - 1) / BN;
-  const bool c11 = AMODE == OP_PLAIN && p.conv1x1;
+  p.tilesN = r.tilesN;
+  p.depi = r.depi;
+  const bool c11 = r.c11;
   void (*fn)(GemmK);
   if constexpr (AMODE == OP_PLAIN) fn = c11 ? pipe_conv1x1_kernel<BM, BN, WM, NS, bf16> : pipe_kernel<AMODE, BM, BN, WM, NS, bf16>;
   else fn = pipe_kernel<AMODE, BM, BN, WM, NS, bf16>;
@@ -441,109 +438,34 @@ int launch_pipe(const GemmK& k, int batch, hipStream_t st) {
     if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }      // (leave no stale error behind for the next launch check)
     attr_done[c11] = true;
   }
-  dim3 grid(tilesM * p.tilesN, 1, batch);
-  ++g_pipe_launches;
-  static const int depi = tune_env("GPV_GLDS_DEPI", 1);
-  p.depi = depi;
-  hipLaunchKernelGGL(fn, grid, dim3(NT), lds, st, p);
+  ++g_knobs.n_pipe;
+  hipLaunchKernelGGL(fn, dim3(r.gx, r.gy, r.gz), dim3(NT), lds, st, p);
   GPV_CHECK_LAUNCH();
   return 0;
 }
 
-// tile configurations: index -> (BM, BN, WM)
-struct PipeCfg { int bm, bn; };
-constexpr PipeCfg kCfgs[] = {{256, 128}, {192, 128}, {128, 128}, {160, 256}, {128, 256}, {96, 256},
-                             {64, 64}, {32, 64}};     // the last two: small-M tiles, 6 / 8 stages, plain GEMMs only
-constexpr int kNumBig = 6;
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-
+// tile configurations: gemm_route.h kCfgs, index -> (BM, BN, WM, stages)
 template <int AMODE>
-int launch_cfg_idx(int idx, const GemmK& k, int batch, hipStream_t st) {
-  switch (idx) {
-    case 0: return launch_pipe<AMODE, 256, 128, 4, 3>(k, batch, st);
-    case 1: return launch_pipe<AMODE, 192, 128, 4, 3>(k, batch, st);
-    case 2: return launch_pipe<AMODE, 128, 128, 2, 3>(k, batch, st);
-    case 3: return launch_pipe<AMODE, 160, 256, 2, 3>(k, batch, st);
-    case 4: return launch_pipe<AMODE, 128, 256, 2, 3>(k, batch, st);
-    case 5: return launch_pipe<AMODE, 96, 256, 2, 3>(k, batch, st);
+int launch_cfg_idx(const GemmK& k, const Route& r, hipStream_t st) {
+  switch (r.cfg) {
+    case 0: return launch_pipe<AMODE, 256, 128, 4, 3>(k, r, st);
+    case 1: return launch_pipe<AMODE, 192, 128, 4, 3>(k, r, st);
+    case 2: return launch_pipe<AMODE, 128, 128, 2, 3>(k, r, st);
+    case 3: return launch_pipe<AMODE, 160, 256, 2, 3>(k, r, st);
+    case 4: return launch_pipe<AMODE, 128, 256, 2, 3>(k, r, st);
+    case 5: return launch_pipe<AMODE, 96, 256, 2, 3>(k, r, st);
   }
   if constexpr (AMODE == OP_PLAIN) {
-    if (idx == 6) return launch_pipe<OP_PLAIN, 64, 64, 2, 6>(k, batch, st);
-    if (idx == 7) return launch_pipe<OP_PLAIN, 32, 64, 2, 8>(k, batch, st);
+    if (r.cfg == 6) return launch_pipe<OP_PLAIN, 64, 64, 2, 6>(k, r, st);
+    if (r.cfg == 7) return launch_pipe<OP_PLAIN, 32, 64, 2, 8>(k, r, st);
   }
-  return -1;
-}
-
-int g_pipe_small = tune_env("GPV_PIPE_SMALL", 1);   // the small-M configurations (64 x 64 / 32 x 64, 6 / 8 stages)
-int g_pipe_mode = tune_env("GPV_PIPE", 1);   // 0 off, 1 heuristic, 100+i: force configuration i wherever legal
-
-// rounds of 256 CUs a configuration needs, weighted by the tile's MFMA work; ties go to the larger tile (operand reuse)
-int pick_cfg(const GemmK& k, int batch) {
-  double best = 1e300;
-  int bi = -1;
-  for (int i = 0; i < kNumBig; ++i) {
-    const int bm = kCfgs[i].bm, bn = kCfgs[i].bn;
-    if (k.N % bn != 0) continue;
-    const int64_t tiles = (int64_t)((k.M + bm - 1) / bm) * (k.N / bn) * batch;
-    const int64_t rounds = (tiles + 255) / 256;
-    // cost of a round ~ MFMA work of a tile + a term for the operand bytes it pulls from L2 (both per k-tile) + fixed per-tile overhead
-    const double per_kt = (double)bm * bn / 16384.0 * 4.0 + (double)(bm + bn) * 128.0 / 56.0 / 16.0 * 0.5;
-    const double cost = (double)rounds * (per_kt * (k.K / 64) + 40.0);
-    if (cost < best - 1e-9) { best = cost; bi = i; }
-  }
-  return bi;
+  return (int)hipErrorInvalidValue;
 }
 
 }  // namespace
 
-int pipe_try_launch(const GemmK& k, int amode, int dtype_in, int dtype_out, int batch, hipStream_t st) {
-  const int mode = g_pipe_mode;
-  if (mode == 0 || dtype_in != GPV_BF16 || dtype_out != GPV_BF16) return -1;
-  if (k.accumulate || k.split_k > 1) return -1;
-  if (k.K % GBK != 0 || k.K < 2 * GBK || k.N % 64 != 0) return -1;
-  if (!al16(k.A) || !al16(k.B) || k.ldb % 8 != 0 || (batch > 1 && (k.sA % 8 != 0 || k.sB % 8 != 0))) return -1;
-  const int64_t lim = 0x7ffffff0ll / 2;
-  if ((int64_t)k.N * k.ldb >= lim) return -1;
-  if (amode == OP_CONV) {
-    if ((int64_t)k.cg.IH * k.cg.IW * k.cg.Cs * ((int64_t)k.M / ((int64_t)k.cg.OH * k.cg.OW) + 1) >= lim) return -1;
-    if (k.cg.Cin % GBK != 0 || k.cg.Cs % 8 != 0) return -1;
-  } else if (amode == OP_PLAIN) {
-    if (k.lda % 8 != 0 || (int64_t)k.M * k.lda >= lim) return -1;
-  } else {
-    return -1;
-  }
-  if (mode < 100 && glds_two_per_cu(k, batch)) return -1;       // (gemm_glds.hip takes these: two half-width tiles per CU)
-  int idx;
-  if (mode >= 100) {
-    idx = mode - 100;
-    if (idx >= kNumCfgs || k.N % kCfgs[idx].bn != 0 || (idx >= kNumBig && amode != OP_PLAIN)) return -1;
-  } else if (g_pipe_small && !k.no_small && amode == OP_PLAIN && !k.conv1x1 && k.K >= 256 &&
-             (int64_t)((k.M + 63) / 64) * (k.N / 64) * batch <= 250 &&
-             ((int64_t)((k.M + 63) / 64) * (k.N / 64) * batch >= 100 || k.K <= 1024)) {
-    // small-M GEMMs (BERT and the co-attention text stream at M = 192, the text decoder at 640 rows): too few 64x64 tiles to
-    // fill the chip.  6-8 k-tiles in flight through LDS-DMA instead of gemm_skinny.hip's one register-staged tile of
-    // look-ahead: 9.0 -> 8.4 us (192x768x768), 10.6 -> 8.8 (192x2304x768), 19.0 -> 16.5 (3200x256x2048) -- modest: what
-    // bounds these launches is the ~35 GB/s per CU of the operand path times the few CUs they occupy, not the look-ahead
-    // (tools/bench_pipe.py small).  Very few tiles with a long reduction (192x768x3072) keep the in-block k-split of gemm_skinny.
-    const int64_t t64 = (int64_t)((k.M + 63) / 64) * (k.N / 64) * batch;
-    idx = t64 < 128 ? 7 : 6;
-  } else {
-    // Where it wins (tools/bench_pipe.py, B=32 shapes, round 2): reductions of >= 512 over 256..768-wide outputs of <= 40 k rows
-    // (layer3/4 3x3 and long-K 1x1 convs fwd + dgrad, the DETR / co-attention GEMMs) and any width below 9600 rows.  N = 128
-    // (layer2) and the >= 1024-wide outputs of >= 9600 rows stay on the two-blocks-per-CU 128x128 kernel (its 600-2400 tiles
-    // balance better than 256-row rounds); the stride-2 dgrad parity classes are too uneven for one block per CU.
-    if (k.K < 512 || k.M < 2048 || k.M > 40000 || k.N < 256) return -1;
-    if (amode == OP_CONV && k.cg.cm) return -1;
-    if (k.N >= 1024 && k.M >= 9600) return -1;
-    if ((int64_t)k.M * k.N * batch > (int64_t)24 << 20) return -1;          // >= 1024 tiles of 256x256: the 8-wave 256x256 kernel (128 flop per operand byte)
-    idx = pick_cfg(k, batch);
-    if (idx < 0) return -1;
-  }
-  return amode == OP_CONV ? launch_cfg_idx<OP_CONV>(idx, k, batch, st) : launch_cfg_idx<OP_PLAIN>(idx, k, batch, st);
+int pipe_launch(const GemmK& k, const Route& r, hipStream_t st) {
+  return r.amode == OP_CONV ? launch_cfg_idx<OP_CONV>(k, r, st) : launch_cfg_idx<OP_PLAIN>(k, r, st);
 }
-
-int pipe_set_mode(int v) { const int prev = g_pipe_mode; g_pipe_mode = v; return prev; }
-int pipe_set_small(int v) { const int prev = g_pipe_small; g_pipe_small = v; return prev; }
-long pipe_launches(long set) { const long prev = g_pipe_launches; if (set >= 0) g_pipe_launches = set; return prev; }
 
 }  // namespace gpvk

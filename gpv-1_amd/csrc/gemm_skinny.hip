@@ -12,12 +12,8 @@
 
 namespace gpvk {
 
-int g_skinny_mode = 1;        // gpv_set_option(GPV_OPT_SKINNY, .): 0 never, 1 heuristic, 2 wherever legal
-
 namespace {
 
-constexpr int SBM = 64, SBN = 64, SBK = 128, SPITCH = SBK + 8;     // LDS row pitch 272 B: 16 rows cover all 64 banks
-constexpr int TPITCH = SBN + 16;      // reduction-major B tile [128 red][64 cols]: pitch 160 B (the transpose-read rule of gemm.hip)
 
 // fragment of a reduction-major tile for the 16 columns starting at cbase: lane (col = lane&15, g = lane>>4) receives the
 // reduction rows 8g..8g+7 of its column (two ds_read_b64_tr_b16, see gemm.hip TStage::frag)
@@ -233,18 +229,14 @@ __global__ __launch_bounds__(256) void skinny_kernel(GemmK p) {
   }
 }
 
-int g_skinny_tile = tune_env("GPV_SKINNY_TILE", 0);     // tuning build: 0 = by cost, 1 = 64 x 64, 2 = 32 x 64, 3 = 32 x 32
-
 template <typename TOut, bool BT, int BM, int BN>
-int launch_skinny_tile(const GemmK& k, hipStream_t st) {
+int launch_skinny_tile(const GemmK& k, const Route& r, hipStream_t st) {
   constexpr size_t stage = (size_t)2 * (BM * SPITCH + (BT ? SBK * TPITCH : BN * SPITCH)) * 2;      // two stages x (A, B) tiles
   constexpr size_t redb = (size_t)4 * BM * BN * 4;
   constexpr size_t lds = stage > redb ? stage : redb;
   GemmK p = k;
-  p.tilesN = (p.N + BN - 1) / BN;
-  const int tilesM = (p.M + BM - 1) / BM;
-  const int nk = (p.K + SBK - 1) / SBK;
-  auto fn = nk >= 2 ? skinny_kernel<TOut, BT, 2, BM, BN> : skinny_kernel<TOut, BT, 1, BM, BN>;
+  p.tilesN = r.tilesN;
+  auto fn = r.cfg == 2 ? skinny_kernel<TOut, BT, 2, BM, BN> : skinny_kernel<TOut, BT, 1, BM, BN>;
   static bool attr_done = false;
   if (!attr_done) {
     for (auto f : {skinny_kernel<TOut, BT, 1, BM, BN>, skinny_kernel<TOut, BT, 2, BM, BN>}) {
@@ -253,28 +245,16 @@ int launch_skinny_tile(const GemmK& k, hipStream_t st) {
     }
     attr_done = true;
   }
-  hipLaunchKernelGGL(fn, dim3(tilesM * p.tilesN), dim3(256), lds, st, p);
+  hipLaunchKernelGGL(fn, dim3(r.gx), dim3(r.block), lds, st, p);
   GPV_CHECK_LAUNCH();
   return 0;
 }
 
-// Tile by measurement (tools/bench_skinny_pf.py, tools/ab_skinny_pf.sh; us at 64 x 64 | 32 x 64 | 32 x 32):
-//   300 x 256 x 2048 (20 tiles of 64 x 64) 14.2 | 10.4 | 7.8     100 x 768 x 3072 (24) 18.3 | 13.3 | 9.9     192 x 768 x 3072 (36) 18.3 | 13.2 | 11.3
-//   640 x 768 x 768 (120) 8.6 | 9.5 | 8.4     640 x 768 x 2048 (120) 15.3 | 15.6 | 15.3 (126 MB through L2 at 32 x 32: the L2s bound it)
-//   640 x 2304 x 768 (360) 12.5 | 11.0 | 12.3     640 x 2048 x 768 (320) 12.0 | 10.6 | 10.8     192 x 3072 x 768 (144) 8.4 | 9.1 | 8.4
-//   reduction-major B: 640 x 768 x 2048 16.8 | 12.6     640 x 768 x 2304 18.1 | 13.6     3200 x 256 x 2048 (200) 20.1 | 16.3
-// i.e. up to ~ 160 tiles of 64 x 64 the smallest tile (4 x as many CUs, half the bytes each), above that 32 x 64 (two co-resident blocks
-// per CU); batch-1 inference 4.88 -> 4.5 - 4.7 ms, train step -0.2 ms (same box, alternating twice).
 template <typename TOut, bool BT>
-int launch_skinny(const GemmK& k, hipStream_t st) {
-  int pick = g_skinny_tile;
-  if (pick == 0) {
-    const int64_t t64 = (int64_t)((k.M + 63) / 64) * ((k.N + 63) / 64);
-    pick = (!BT && t64 <= 160) ? 3 : 2;
-  }
-  if (pick == 2) return launch_skinny_tile<TOut, BT, 32, 64>(k, st);
-  if constexpr (!BT) { if (pick == 3) return launch_skinny_tile<TOut, BT, 32, 32>(k, st); }
-  return launch_skinny_tile<TOut, BT, 64, 64>(k, st);
+int launch_skinny(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.bm == 32 && r.bn == 64) return launch_skinny_tile<TOut, BT, 32, 64>(k, r, st);
+  if constexpr (!BT) { if (r.bm == 32) return launch_skinny_tile<TOut, BT, 32, 32>(k, r, st); }
+  return launch_skinny_tile<TOut, BT, 64, 64>(k, r, st);
 }
 
 // ---- weight-gradient form: C[M,N] (+)= A^T B with A [K][M], B [K][N] both reduction-major (dW = dY^T X) -------------
@@ -400,58 +380,26 @@ __global__ __launch_bounds__(256) void skinny_tt_kernel(GemmK p) {
 
 }  // namespace
 
-// returns 0 = launched, -1 = not applicable, > 0 = hipError_t.  b_trans: B is reduction-major (GPV_TRANS): dX = dY W.
-int skinny_try_launch(const GemmK& k, int b_trans, int dtype_in, int dtype_out, int batch, hipStream_t st) {
-  if (g_skinny_mode == 0 || dtype_in != GPV_BF16 || batch != 1 || k.accumulate || k.split_k > 1) return -1;
-  if (k.K % 8 != 0 || k.lda % 8 != 0 || k.ldb % 8 != 0 || !al16(k.A) || !al16(k.B)) return -1;
-  if (b_trans && k.N % 8 != 0) return -1;
-  {   // 32-bit byte offsets into each operand
-    const int64_t lim = 0x7ffffff0ll / 2;
-    if ((int64_t)k.M * k.lda >= lim || (int64_t)(b_trans ? k.K : k.N) * k.ldb >= lim) return -1;
-  }
-  if (g_skinny_mode == 1) {
-    // measured on every forward GEMM shape of the step (tools/bench_step_gemms.py, SK=0 vs 2): it wins whenever the
-    // 64x64 tiles cannot fill the chip (<= ~1.4 per CU), and up to 2.5 per CU when the reduction is long
-    const int64_t tiles = (int64_t)((k.M + SBM - 1) / SBM) * ((k.N + SBN - 1) / SBN);
-    // (the 360..640-tile, K >= 2048 launches -- 9600x256x2048, 3200x768x3072 -- go to the 4-wave direct-to-LDS kernel when B
-    // is k-major: 54 -> 30 us, 52 -> 40 us; that kernel has no reduction-major B form, so dX = dY W keeps them here)
-    if (!((tiles <= 360 && k.K >= 128) || (b_trans && tiles <= 640 && k.K >= 2048))) return -1;
-  }
-  if (b_trans) return dtype_out == GPV_BF16 ? launch_skinny<bf16, true>(k, st) : launch_skinny<float, true>(k, st);
-  return dtype_out == GPV_BF16 ? launch_skinny<bf16, false>(k, st) : launch_skinny<float, false>(k, st);
+int skinny_launch(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.bmode == OP_TRANS) return r.dt_out == GPV_BF16 ? launch_skinny<bf16, true>(k, r, st) : launch_skinny<float, true>(k, r, st);
+  return r.dt_out == GPV_BF16 ? launch_skinny<bf16, false>(k, r, st) : launch_skinny<float, false>(k, r, st);
 }
 
-// weight-gradient form; returns 0 = launched, -1 = not applicable
-int skinny_tt_try_launch(const GemmK& k, int dtype_in, int dtype_out, int batch, hipStream_t st) {
-  if (g_skinny_mode == 0 || dtype_in != GPV_BF16 || dtype_out != GPV_F32 || batch != 1 || !k.accumulate) return -1;
-  if (k.M % 8 != 0 || k.N % 8 != 0 || k.lda % 8 != 0 || k.ldb % 8 != 0 || k.ldc % 4 != 0) return -1;
-  if (!al16(k.A) || !al16(k.B) || !al16(k.C) || k.res || k.mask || k.bias || k.act || k.dthresh) return -1;
-  if ((int64_t)k.K * k.lda >= 0x7ffffff0ll / 2 || (int64_t)k.K * k.ldb >= 0x7ffffff0ll / 2) return -1;   // 32-bit byte offsets
-  const int64_t tiles = (int64_t)((k.M + SBM - 1) / SBM) * ((k.N + SBN - 1) / SBN);
-  const int nk = (k.K + SBK - 1) / SBK;
-  if (g_skinny_mode == 1 && (tiles > 256 || nk < 4)) return -1;
-  // enough splits for ~512 blocks, at least 3 k-steps of 128 each, within the lent workspace
-  int split = (int)((512 + tiles - 1) / tiles);
-  if (split > nk / 3) split = nk / 3;
-  if (split < 1) split = 1;
-  while (split > 1 && (k.ws_base == nullptr || (int64_t)split * k.M * k.N * 4 > k.ws_bytes)) --split;
+// weight-gradient form
+int skinny_tt_launch(const GemmK& k, const Route& r, hipStream_t st) {
   GemmK p = k;
-  p.tilesN = (p.N + SBN - 1) / SBN;
-  p.kt_per_split = (nk + split - 1) / split;
-  split = (nk + p.kt_per_split - 1) / p.kt_per_split;
-  p.ws = split > 1 ? reinterpret_cast<float*>(k.ws_base) : nullptr;
-  constexpr size_t stage = (size_t)2 * 2 * SBK * TPITCH * 2;
-  constexpr size_t redb = (size_t)4 * SBM * SBN * 4;
-  constexpr size_t lds = stage > redb ? stage : redb;
+  p.tilesN = r.tilesN;
+  p.kt_per_split = r.kt_per_split;
+  p.ws = r.two_pass ? reinterpret_cast<float*>(k.ws_base) : nullptr;
   static bool attr_done = false;
   if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(skinny_tt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(skinny_tt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
     if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }      // (leave no stale error behind for the next launch check)
     attr_done = true;
   }
-  hipLaunchKernelGGL(skinny_tt_kernel, dim3((unsigned)tiles, split), dim3(256), lds, st, p);
+  hipLaunchKernelGGL(skinny_tt_kernel, dim3(r.gx, r.gy), dim3(r.block), (size_t)r.lds, st, p);
   GPV_CHECK_LAUNCH();
-  if (split > 1) return launch_splitk_reduce(p.ws, split, p.M, p.N, reinterpret_cast<float*>(p.C), p.ldc, st);
+  if (r.two_pass) return launch_splitk_reduce(p.ws, r.split, p.M, p.N, reinterpret_cast<float*>(p.C), p.ldc, st);
   return 0;
 }
 

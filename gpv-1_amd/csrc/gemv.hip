@@ -10,9 +10,6 @@
 
 namespace gpvk {
 
-int g_gemv_mode = 1;          // gpv_set_option(GPV_OPT_GEMV, .): 0 never, 1 (default) wherever legal
-long g_gemv_launches = 0;
-
 namespace {
 
 template <typename TI, typename TO, int MR, int NW>
@@ -66,24 +63,22 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemmK p) {
 }
 
 template <typename TI, typename TO, int MR>
-int launch_nw(const GemmK& k, hipStream_t st) {
-  // columns per wave: as few as keep >= 256 workgroups (one per CU) busy
-  const int nw = k.N >= 4096 ? 4 : (k.N >= 2048 ? 2 : 1);
-  const dim3 block(256);
-  if (nw == 4) gemv_kernel<TI, TO, MR, 4><<<dim3((k.N + 15) / 16), block, 0, st>>>(k);
-  else if (nw == 2) gemv_kernel<TI, TO, MR, 2><<<dim3((k.N + 7) / 8), block, 0, st>>>(k);
-  else gemv_kernel<TI, TO, MR, 1><<<dim3((k.N + 3) / 4), block, 0, st>>>(k);
-  ++g_gemv_launches;
+int launch_nw(const GemmK& k, const Route& r, hipStream_t st) {
+  const dim3 grid(r.gx), block(r.block);
+  if (r.bn == 4) gemv_kernel<TI, TO, MR, 4><<<grid, block, 0, st>>>(k);
+  else if (r.bn == 2) gemv_kernel<TI, TO, MR, 2><<<grid, block, 0, st>>>(k);
+  else gemv_kernel<TI, TO, MR, 1><<<grid, block, 0, st>>>(k);
+  ++g_knobs.n_gemv;
   const hipError_t e = hipGetLastError();
   return (int)e;
 }
 
 template <typename TI, typename TO>
-int launch_mr(const GemmK& k, hipStream_t st) {
-  if (k.M == 1) return launch_nw<TI, TO, 1>(k, st);
-  if (k.M == 2) return launch_nw<TI, TO, 2>(k, st);
-  if (k.M <= 4) return launch_nw<TI, TO, 4>(k, st);
-  return launch_nw<TI, TO, 8>(k, st);
+int launch_mr(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.bm == 1) return launch_nw<TI, TO, 1>(k, r, st);
+  if (r.bm == 2) return launch_nw<TI, TO, 2>(k, r, st);
+  if (r.bm == 4) return launch_nw<TI, TO, 4>(k, r, st);
+  return launch_nw<TI, TO, 8>(k, r, st);
 }
 
 // one workgroup of 1024 threads per row: the index of the largest x[r, v] + addend[v]; equal values -> the lowest index; NaNs
@@ -443,16 +438,9 @@ int launch_ln_mr(const LnGemvK& k, hipStream_t st) {
 
 }  // namespace
 
-// returns 0 = launched, -1 = not applicable, > 0 = hipError_t
-int gemv_try_launch(const GemmK& k, int dtype_in, int dtype_out, int batch, hipStream_t st) {
-  if (g_gemv_mode == 0 || g_kernel_forced || k.M > 8 || batch != 1 || k.accumulate || k.split_k > 1) return -1;
-  if (k.rowscale || k.mask || k.dthresh || k.a_rowsum) return -1;
-  if (k.M > 2 && k.N >= 4096) return -1;            // 4 columns x > 2 rows per wave: the tile kernels are faster (tools/bench_gemv.py)
-  if (k.K % 8 != 0 || k.lda % 8 != 0 || k.ldb % 8 != 0 || !al16(k.A) || !al16(k.B)) return -1;
-  if (dtype_in == GPV_BF16 && dtype_out == GPV_BF16) return launch_mr<bf16, bf16>(k, st);
-  if (dtype_in == GPV_BF16 && dtype_out == GPV_F32) return launch_mr<bf16, float>(k, st);
-  if (dtype_in == GPV_F32 && dtype_out == GPV_F32) return launch_mr<float, float>(k, st);
-  return -1;
+int gemv_launch(const GemmK& k, const Route& r, hipStream_t st) {
+  if (r.dt_in == GPV_BF16) return r.dt_out == GPV_BF16 ? launch_mr<bf16, bf16>(k, r, st) : launch_mr<bf16, float>(k, r, st);
+  return launch_mr<float, float>(k, r, st);
 }
 
 }  // namespace gpvk
