@@ -26,10 +26,15 @@ LIBRARIES = {l.key: l for l in (
 EXTENSIONS = {l.key: l for l in (
     Library('enc', 'libgpv_enc.so', 'gpv_enc.h', 'gpv_enc_', 'JPEG encoder'),
 )}
+# Libraries added since (the Makefile's `addons` target): the same rules, build checks and loader; a third table because the ABI tests
+# pin the contents of the two above.
+ADDONS = {l.key: l for l in (
+    Library('phrase', 'libgpv_phrase.so', 'gpv_phrase.h', 'gpv_phrase_', 'phrase search'),
+)}
 
 
 def library(key):
-    return LIBRARIES[key] if key in LIBRARIES else EXTENSIONS[key]
+    return LIBRARIES[key] if key in LIBRARIES else EXTENSIONS[key] if key in EXTENSIONS else ADDONS[key]
 
 
 def module_name(key):

@@ -70,6 +70,31 @@ def create_vocab_mask(model, classes=COCO_CLASSES, synonyms=None, use_syns=False
     return tokens, mask
 
 
+def create_phrase_set(model, classes=COCO_CLASSES, synonyms=None, use_syns=False):
+    """the closed answer set of classification as whole phrases -> (phrases.PhraseSet, phrase_to_class): phrase i names
+    classes[phrase_to_class[i]].  With synonyms (the table create_vocab_mask takes) several phrases map to one class and a class
+    without an entry is left out, as in the mask.  Unlike the mask nothing is dropped silently: a word outside the model's
+    vocabulary is a ValueError, and so is a name that two classes share."""
+    from .phrases import PhraseSet
+    texts, owner, seen = [], [], {}
+    for ci, cls in enumerate(classes):
+        names = [cls]
+        if use_syns and synonyms is not None:
+            if cls not in synonyms:
+                continue
+            names = synonyms[cls]
+        for name in names:
+            key = tuple(word_tokenize(name))
+            if key in seen:
+                if seen[key] != ci:
+                    raise ValueError(f'create_phrase_set: {name!r} names both {classes[seen[key]]!r} and {cls!r}')
+                continue
+            seen[key] = ci
+            texts.append(name)
+            owner.append(ci)
+    return PhraseSet.from_texts(model, texts), owner
+
+
 class BoxesWriter:
     """one group per sample id: 'boxes' [Q,4] float32, 'relevance' [Q] float32"""
 
@@ -112,12 +137,21 @@ def boxes_to_h5py(npz_path, h5py_path):
 
 @torch.no_grad()
 def make_predictions(model, batches, eval_dir, task, subset='val', data_split='original_split', num_eval_batches=None,
-                     vocab_mask=None, beam_size=None, beam=None):
+                     vocab_mask=None, beam_size=None, beam=None, answer_set=None, classes=COCO_CLASSES):
     """compute_predictions.py:30-85; returns (predictions dict, json path, boxes path).  beam_size / beam (added keys, as in
     inference.predict: beam.impl, beam.finished, beam.length_penalty): answers by beam search instead of greedy decoding; a vocabulary
-    mask then needs beam.impl = device (GPV.forward_beam_search)"""
+    mask then needs beam.impl = device (GPV.forward_beam_search).  answer_set (added): None / 'tokens' is the reference's flat
+    vocabulary mask, unchanged; 'phrases' answers from the closed set of `classes` (create_phrase_set; GPV.forward_beam_search with
+    phrases=, beam_size default 4): every answer written is one of the class names"""
     dev = model.vision_token.device
-    if vocab_mask is None and task == 'CocoClassification':
+    if answer_set not in (None, 'tokens', 'phrases'):
+        raise ValueError(f"make_predictions: answer_set must be 'tokens' or 'phrases', got {answer_set!r}")
+    pset = owner = None
+    if answer_set == 'phrases':
+        if vocab_mask is not None:
+            raise ValueError("make_predictions: answer_set='phrases' and vocab_mask exclude each other")
+        pset, owner = create_phrase_set(model, classes)
+    if vocab_mask is None and task == 'CocoClassification' and pset is None:
         vocab_mask = create_vocab_mask(model)[1]
     if vocab_mask is not None:
         vocab_mask = torch.as_tensor(vocab_mask, dtype=torch.float32, device=dev)
@@ -130,12 +164,17 @@ def make_predictions(model, batches, eval_dir, task, subset='val', data_split='o
             break
         if not isinstance(imgs, NestedTensor):
             imgs = nested_tensor_from_tensor_list([x.to(dev) for x in imgs])
-        if beam_size:
+        chosen = None
+        if pset is not None:
+            outputs = model.forward_beam_search(imgs, queries, beam_size=beam_size or 4, phrases=pset,
+                                                length_penalty=(beam or {}).get('length_penalty'))
+            chosen = outputs['_beam_phrase'][:, 0].cpu().tolist()
+        elif beam_size:
             outputs = model.forward_beam_search(imgs, queries, beam_size=beam_size, vocab_mask=vocab_mask, **beam_options(beam))
         else:
             outputs = model(imgs, queries, None, vocab_mask=vocab_mask)
-        for sid, d in zip(sample_ids, decode_outputs(outputs, model, num_output_boxes=None)):
-            predictions[sid] = {'answer': d['answer']}
+        for j, (sid, d) in enumerate(zip(sample_ids, decode_outputs(outputs, model, num_output_boxes=None))):
+            predictions[sid] = {'answer': d['answer'] if chosen is None else classes[owner[chosen[j]]]}
             boxes_file.add(sid, d['boxes'], d['relevance'])
     boxes_path = boxes_file.close()
     json_path = os.path.join(eval_dir, f'{task}_{data_split}_{subset}_predictions.json')

@@ -541,14 +541,19 @@ class GPV(nn.Module):
         return impl, finished, alpha
 
     @torch.no_grad()
-    def forward_beam_search(self, images, queries, beam_size=1, vocab_mask=None, impl=None, finished=None, length_penalty=None):
+    def forward_beam_search(self, images, queries, beam_size=1, vocab_mask=None, impl=None, finished=None, length_penalty=None, phrases=None):
         # (no GPV_OPT_PIPE_SMALL override here: the 320-row GEMMs of beam 5 x batch 64 want the small-M configurations -- 26.0 against 36.8 ms per batch)
         """gpv.py:209-362, quirks preserved (no length normalisation, finished beams keep extending --
         the reference's `is True` test never fires --, last seqs slot never written, stable tie order).
         impl='device' (or cfg beam.impl / GPV_BEAM=device) runs every step's selection and the cache reorder as two HIP launches
         (hip_beam; the rule: gpv1_amd.beam) and is the only path that knows finished='freeze' (a hypothesis that emitted __stop__
         keeps its score and is followed by __pad__), length_penalty (alpha of ((5 + len) / 6) ** alpha; the ranking key, not the
-        reported probability) and vocab_mask ([V] fp32 added to every row of logits)."""
+        reported probability) and vocab_mask ([V] fp32 added to every row of logits).
+        phrases (a phrases.PhraseSet): the answer is one of the set's phrases -- the device path with gpv_phrase_step (hip_phrase; the
+        rule: gpv1_amd.phrases) in place of gpv_beam_step; '_beam_phrase' [B,K] int32 (the phrase a slot spelled, -1 for a slot
+        that holds none) is added, 'answer_probs' are the model's probabilities of phrase + __stop__ over the whole vocabulary."""
+        if phrases is not None:
+            return self._forward_phrases(images, queries, beam_size, phrases, vocab_mask, impl, finished, length_penalty)
         impl, finished, alpha = self._beam_options(impl, finished, length_penalty, vocab_mask)
         kw = dict(impl=impl, finished=finished, alpha=alpha)
         outputs = None
@@ -561,6 +566,10 @@ class GPV(nn.Module):
                                     lambda im, q, vm, qe: self._beam_device(im, q, beam_size, vocab_mask=vm, **kw), images, queries, vocab_mask)
         if outputs is None:
             outputs = self._beam_device(images, queries, beam_size, vocab_mask=vocab_mask, **kw)
+        return self._beam_answers(outputs)
+
+    def _beam_answers(self, outputs):
+        """'answers' / 'answer_probs' of a finished search: the words of every slot up to __stop__ / __pad__, exp of its score"""
         seqs, seq_lp = outputs.pop('_beam_seqs'), outputs.pop('_beam_lp')
         K, B, T = seqs.shape
         seqs_c, lp = seqs.cpu(), seq_lp.exp().cpu()
@@ -578,6 +587,92 @@ class GPV(nn.Module):
                 answers[b].append(words)
                 probs[b].append(float(lp[b, k]))
         outputs['answers'], outputs['answer_probs'] = answers, probs
+        return outputs
+
+    def _phrase_options(self, beam_size, phrases, vocab_mask, impl, finished, length_penalty):
+        """the checks of a phrase-constrained call, before anything runs -> alpha"""
+        from . import phrases as prule
+        if not isinstance(phrases, prule.PhraseSet):
+            raise ValueError(f'forward_beam_search: phrases must be a phrases.PhraseSet, got {type(phrases).__name__}')
+        if vocab_mask is not None:
+            raise ValueError('forward_beam_search: phrases and vocab_mask exclude each other (the phrase set says which tokens are '
+                             'allowed where; the score is normalised over the whole vocabulary, which a mask would change)')
+        if impl == 'torch':
+            raise ValueError("forward_beam_search: phrases need the device path (impl='torch' is the reference's search and is not taught new rules)")
+        if finished == 'extend':
+            raise ValueError("forward_beam_search: phrases with finished='extend' is a contradiction (a hypothesis that spelled a phrase and "
+                             '__stop__ is done: extending it would leave the set)')
+        w = self.word_to_idx
+        if (phrases.V, phrases.pad_id, phrases.stop_id, phrases.cls_id) != (len(self.vocab), w['__pad__'], w['__stop__'], w['__cls__']):
+            raise ValueError('forward_beam_search: the phrase set was compiled for another vocabulary (size or special ids differ)')
+        prule.check_extents(beam_size, self.cfg.max_text_len, phrases)
+        if self.training or torch.is_grad_enabled() or not self.cfg.get('kv_decode', True):
+            raise RuntimeError('forward_beam_search: phrases need the KV-cached decoder (eval mode, no grad, cfg kv_decode); there is no fallback')
+        return float(length_penalty or 0.0)
+
+    def _forward_phrases(self, images, queries, beam_size, phrases, vocab_mask=None, impl=None, finished=None, length_penalty=None, raw=False):
+        alpha = self._phrase_options(beam_size, phrases, vocab_mask, impl, finished, length_penalty)
+        outputs = None
+        if self.cfg.get('graph_inference', True):
+            queries = self._host_tokenize(images, queries)
+            # the key carries the set's digest; the captured run's outputs hold the set ('_phrase_set'), and with it its device arrays
+            outputs = self._graphed(('phrases', beam_size, alpha, phrases.digest),
+                                    lambda im, q, vm, qe: self._phrase_device(im, q, beam_size, phrases, alpha), images, queries, None)
+        if outputs is None:
+            outputs = self._phrase_device(images, queries, beam_size, phrases, alpha)
+        outputs.pop('_phrase_set', None)
+        if raw:
+            return outputs
+        keep = {k: outputs[k] for k in ('_beam_seqs', '_beam_lp')}
+        outputs = self._beam_answers(outputs)
+        outputs.update(keep)
+        return outputs
+
+    @torch.no_grad()
+    def choose(self, images, queries, phrases, beam_size=4, length_penalty=None):
+        """the best phrase of the set per sample -> (index [B] int64, log_prob [B] fp32) of slot 0, on the device, no sync inside
+        (beyond the one every graphed inference call ends with)"""
+        o = self._forward_phrases(images, queries, beam_size, phrases, length_penalty=length_penalty, raw=True)
+        return o['_beam_phrase'][:, 0].long(), o['_beam_lp'][:, 0].clone()
+
+    def _phrase_device(self, images, queries, beam_size, pset, alpha=0.0):
+        """device part of the phrase-constrained search: outputs dict + '_beam_seqs' [K,B,T] + '_beam_lp' [B,K] + '_beam_phrase' [B,K] int32:
+        per token the decoder core, gpv_phrase_step (writes the next tokens straight into kv.tok) and gpv_beam_reorder -- two launches
+        beside the decoder's, no allocation inside the loop"""
+        from . import beam as rule, hip_phrase
+        from .decode import GreedyKVDecoder
+        graphed = isinstance(queries, (tuple, list)) and len(queries) == 2 and all(torch.is_tensor(q) for q in queries) and \
+            hasattr(images, 'tensors') and images.tensors.is_cuda and torch.cuda.is_current_stream_capturing()
+        outputs, memory = self._encode(images, queries, self._bert_fork(images, queries) if graphed else None)
+        B, K, T = memory.shape[0], beam_size, self.cfg.max_text_len
+        dev = memory.device
+        memK = memory.repeat(K, 1, 1)
+        key = (K * B, memK.shape[1], str(dev), RT.dtype, 'beam')
+        kv = self._kvdec.get(key)
+        if kv is None:
+            kv = self._kvdec[key] = GreedyKVDecoder(self, K * B, memK.shape[1], use_graphs=False)
+        kv.memory.copy_(memK.reshape(K * B * memK.shape[1], -1))
+        kv._prepare()
+        inv_pen = None
+        if alpha != 0.0:
+            tables = self.__dict__.setdefault('_beam_tables', {})            # (filled by the warm-up runs: a capture finds it on the device)
+            inv_pen = tables.get((T, alpha, str(dev)))
+            if inv_pen is None:
+                inv_pen = tables[(T, alpha, str(dev))] = torch.from_numpy(rule.length_table(T, alpha)).to(dev)
+        pset.device_arrays(dev)                                              # (made once per device, by the warm-up runs of a capture)
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+        seq_lp = torch.zeros(B, K, device=dev)
+        seqs = torch.zeros(K, B, T, dtype=torch.long, device=dev)
+        lse = torch.zeros(K * B, device=dev)
+        parent, node, length = i32(B, K), i32(B, K), i32(B, K)
+        phrase = torch.full((B, K), -1, dtype=torch.int32, device=dev)
+        kv.tok.fill_(self.word_to_idx['__cls__'])
+        for t in range(T - 1):
+            hip_phrase.step(kv._step_core(t), lse, seq_lp, seqs, kv.tok, parent, node, phrase, length, t, pset, inv_pen=inv_pen)
+            if t + 1 < T - 1:                                                  # (nothing reads the caches after the last step)
+                kv.reorder_device(parent, t + 1)
+        outputs['_beam_seqs'], outputs['_beam_lp'], outputs['_beam_phrase'] = seqs, seq_lp, phrase
+        outputs['beam_lengths'], outputs['_phrase_set'] = length, pset
         return outputs
 
     def _beam_device(self, images, queries, beam_size, vocab_mask=None, impl='torch', finished='extend', alpha=0.0):

@@ -12,6 +12,7 @@ punctuation-attachment rules (a join that glues ``, . ! ? ; : ' n't 's %`` to th
 usage: python -m gpv1_amd.inference [--config some.yaml] ckpt=... inputs.img=img.npy inputs.query="what is this?"
                                       [beam_size=5] [num_output_boxes=5]
                                       [beam.impl=device] [beam.finished=freeze] [beam.length_penalty=0.6]
+                                      [inputs.answers="cat|dog|traffic light"]
                                       [outputs.vis=picture.jpg]
 ``outputs.vis`` (the reference's ``inference_util.vis_sample``): the picture the model saw with the ``num_output_boxes`` boxes drawn,
 encoded on the device (gpv1_amd.jpeg_encode.DeviceJpegEncoder) and written to that path.
@@ -124,15 +125,29 @@ def beam_options(beam):
 
 
 @torch.no_grad()
-def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=None, beam=None):
+def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=None, beam=None, answers=None):
     """images: list of arrays/tensors (see preprocess_image); queries: list[str] or (ids, mask) tensors;
     size: (H, W) to resize HxWx3 arrays to first (the data loader's 480x640), None = as they are (inference.py).  Any image size
     runs: the batch is padded to its largest image and the encoder attends over ceil(H / 32) ceil(W / 32) tokens (850 for
-    800x1088), beyond 320 of them on the streaming attention kernels"""
+    800x1088), beyond 320 of them on the streaming attention kernels.  answers (added): a list of answer texts -- the answer is one of
+    them (phrases.PhraseSet, GPV.forward_beam_search with phrases=, beam_size default min(4, len(answers))): 'answer' is the chosen
+    text, 'answer_log_prob' the model's log-probability of it followed by __stop__, 'runners_up' the other slots' (text, log_prob)"""
     dev = model.vision_token.device
     if size is not None:
         images = [resize_image(i, size) if not torch.is_tensor(i) else i for i in images]
     imgs = nested_tensor_from_tensor_list([preprocess_image(i).to(dev) for i in images])
+    if answers:
+        from .phrases import PhraseSet
+        answers = list(answers)
+        pset = PhraseSet.from_texts(model, answers)
+        out = model.forward_beam_search(imgs, queries, beam_size=beam_size or min(4, len(answers)), phrases=pset,
+                                        length_penalty=(beam or {}).get('length_penalty'))
+        phrase, lp = out['_beam_phrase'].cpu().tolist(), out['_beam_lp'].cpu().tolist()
+        decoded = decode_outputs(out, model, num_output_boxes)
+        for b, d in enumerate(decoded):
+            ranked = [(answers[p], l) for p, l in zip(phrase[b], lp[b]) if p >= 0]
+            d['answer'], d['answer_log_prob'], d['runners_up'] = ranked[0][0], ranked[0][1], ranked[1:]
+        return decoded
     if beam_size:
         out = model.forward_beam_search(imgs, queries, beam_size=beam_size, **beam_options(beam))
     else:
@@ -157,13 +172,14 @@ def main(argv=None):
     ap.add_argument('--config', default=None, help='YAML file (e.g. the reference configs/exp/gpv.yaml); default: gpv1_amd.default_config')
     ap.add_argument('overrides', nargs='*')
     args = ap.parse_args(argv)
-    # outputs.vis= ckpt= inputs.img= inputs.query= beam_size= beam.impl= beam.finished= beam.length_penalty= are added keys
+    # outputs.vis= ckpt= inputs.img= inputs.query= inputs.answers= beam_size= beam.impl= beam.finished= beam.length_penalty= are added keys
     cfg = load_config(args.config, args.overrides, strict=False) if args.config else from_dict(default_tree(), args.overrides, strict=False)
     model = GPV(cfg.model).cuda().eval()
     load_model_state(model, cfg.get('ckpt', cfg.eval.ckpt), map_location='cuda:0')
     img = np.load(cfg.inputs.img)
+    answers = cfg.inputs.get('answers', None)                    # inputs.answers="cat|dog|traffic light": the answer is one of these
     pred = predict(model, [img], [cfg.inputs.query], beam_size=cfg.get('beam_size'), num_output_boxes=cfg.get('num_output_boxes', 5),
-                   beam=cfg.get('beam'))[0]
+                   beam=cfg.get('beam'), answers=[a.strip() for a in str(answers).split('|') if a.strip()] if answers else None)[0]
     for k, v in pred.items():
         print('-' * 80)
         print(k)

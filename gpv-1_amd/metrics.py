@@ -75,11 +75,30 @@ def cap_metrics(model, batches, samples, limit=None, scorer=None):
 
 
 @torch.no_grad()
-def cls_metrics(model, batches, samples, limit=None, synonyms=None):
+def cls_metrics(model, batches, samples, limit=None, synonyms=None, answer_set='tokens', classes=None, beam_size=4):
     """metrics.py:147-199 -> overall accuracy.  synonyms: the reference's {class: [names]} table (data the caller supplies); without
-    it every class answers to its own name only, in the mask and in the scoring"""
-    _, mask = create_vocab_mask(model, synonyms=synonyms, use_syns=synonyms is not None)
-    answers = _answer_loop(model, batches, samples, limit, vocab_mask=mask)
+    it every class answers to its own name only, in the mask and in the scoring.  answer_set (added): 'tokens' confines the greedy
+    decode with the reference's flat vocabulary mask, unchanged; 'phrases' answers from the closed set of whole names
+    (compute_predictions.create_phrase_set over `classes`, default the COCO classes; GPV.choose with `beam_size`): the answer is the
+    class name of the chosen phrase"""
+    if answer_set not in ('tokens', 'phrases'):
+        raise ValueError(f"cls_metrics: answer_set must be 'tokens' or 'phrases', got {answer_set!r}")
+    if answer_set == 'phrases':
+        from .compute_predictions import COCO_CLASSES, create_phrase_set
+        classes = COCO_CLASSES if classes is None else classes
+        pset, owner = create_phrase_set(model, classes, synonyms=synonyms, use_syns=synonyms is not None)
+        dev = _device(model)
+        n = len(samples) if limit is None else min(int(limit), len(samples))
+        model.eval()
+        picks = []
+        for imgs, queries, _ in batches:
+            if sum(len(p) for p in picks) >= n:
+                break
+            picks.append(model.choose(_images(imgs, dev), queries, pset, beam_size=beam_size)[0])
+        answers = [classes[owner[i]] for p in picks for i in p.cpu().tolist()][:n]
+    else:
+        _, mask = create_vocab_mask(model, synonyms=synonyms, use_syns=synonyms is not None)
+        answers = _answer_loop(model, batches, samples, limit, vocab_mask=mask)
     predictions = {str(s['id']): {'answer': a} for s, a in zip(samples, answers)}
     if synonyms is None:
         synonyms = {s['answer']: [s['answer']] for s in samples}
