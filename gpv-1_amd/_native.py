@@ -20,21 +20,9 @@ LIBRARIES = {l.key: l for l in (
     Library('health', 'libgpv_health.so', 'gpv_health.h', 'gpv_health_', 'flight-recorder'),
     Library('beam', 'libgpv_beam.so', 'gpv_beam.h', 'gpv_beam_', 'beam search'),
     Library('huff', 'libgpv_huff.so', 'gpv_huff.h', 'gpv_huff_', 'JPEG entropy'),
-)}
-# Libraries beside the seven (the Makefile's `extensions` target): the same rules, build checks and loader; a table of their own
-# because the number of LIBRARIES is pinned by the ABI tests.
-EXTENSIONS = {l.key: l for l in (
     Library('enc', 'libgpv_enc.so', 'gpv_enc.h', 'gpv_enc_', 'JPEG encoder'),
-)}
-# Libraries added since (the Makefile's `addons` target): the same rules, build checks and loader; a third table because the ABI tests
-# pin the contents of the two above.
-ADDONS = {l.key: l for l in (
     Library('phrase', 'libgpv_phrase.so', 'gpv_phrase.h', 'gpv_phrase_', 'phrase search'),
 )}
-
-
-def library(key):
-    return LIBRARIES[key] if key in LIBRARIES else EXTENSIONS[key] if key in EXTENSIONS else ADDONS[key]
 
 
 def module_name(key):
@@ -42,11 +30,11 @@ def module_name(key):
 
 
 def header_path(key):
-    return os.path.join(ROOT, 'include', library(key).header)
+    return os.path.join(ROOT, 'include', LIBRARIES[key].header)
 
 
 def lib_path(key):
-    return os.path.join(ROOT, 'gpv-1_amd', 'csrc', library(key).file)
+    return os.path.join(ROOT, 'gpv-1_amd', 'csrc', LIBRARIES[key].file)
 
 
 def load(key, signatures, path=None):
@@ -55,7 +43,7 @@ def load(key, signatures, path=None):
     path = path or lib_path(key)
     if not os.path.exists(path):
         raise RuntimeError(
-            f'gpv1_amd: {library(key).noun} kernel library not found at {path}. Build it with '
+            f'gpv1_amd: {LIBRARIES[key].noun} kernel library not found at {path}. Build it with '
             f'`python -c "import __graft_entry__ as g; g.build()"` (make -C gpv-1_amd/csrc). '
             f'There is no CPU/eager fallback by design.')
     lib = C.CDLL(path)

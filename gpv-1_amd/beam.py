@@ -8,12 +8,14 @@ Step t (0 <= t < T-1), batch element b, parent k1 = 0..K-1, logits row r = k1*B 
  3. The row's candidates are its K largest x_v, ties to the lower v; k2 is the rank.  lp = x_v - lse_r: one fp32 subtract.
  4. score(k1,k2) = seq_lp[b,k1] + lp: one fp32 add.  t == 0 and k1 > 0: score = -1e9 exactly.  Mode FREEZE with finished[b,k1] set: the
     parent has exactly one candidate, k2 = 0, token pad_id, score = seq_lp[b,k1] unchanged; its other candidates do not exist.
- 5. key = score * inv_pen[len']: one fp32 multiply, len' = length[b,k1] + (finished[b,k1] ? 0 : 1) (in either mode; clamped to T, the
-    table's last entry).  inv_pen None: key = score.  inv_pen[n] = fp32(((5 + n) / 6) ** -alpha) (length_table).
- 6. Selection: the first K of the candidates sorted by key descending, ties to the lower k1*K + k2 (a stable sort).
+ 5. key = score * inv_pen[len']: one fp32 multiply, len' = length[b,k1] + (finished[b,k1] ? 0 : 1) (in either mode; clamped to 0 .. T,
+    T the table's last entry).  inv_pen None: key = score.  inv_pen[n] = fp32(((5 + n) / 6) ** -alpha) (length_table).
+ 6. Selection: the first K of the candidates sorted by key descending, ties to the lower k1*K + k2 (a stable sort).  With only
+    c < K candidates (gpv1_amd.phrases; never here) the slots c..K-1 take the caller's default: parent 0, its token and state.
  7. Slot k with the chosen (k1, k2, w): parent[b,k] = k1; seq_lp'[b,k] = score (raw, not the key); seqs'[k,b,:t] = seqs[k1,b,:t],
-    seqs'[k,b,t] = w (positions behind t are left alone); tok[k*B+b] = w; finished'[b,k] = FREEZE ? (finished[b,k1] | (w == stop_id)) : 0;
-    length'[b,k] = len'.
+    seqs'[k,b,t] = w (positions behind t are left alone); tok[k*B+b] = w; length'[b,k] = len'; the search's own state, here
+    finished'[b,k] = FREEZE ? (finished[b,k1] | (w == stop_id)) : 0.
+Steps 5-7 are select_slots, shared with gpv1_amd.phrases (on the device: csrc/beam_core.h select_by_rank and write_slots).
 Mode EXTEND without penalty and mask is the reference's search (exp/gpv/models/gpv.py:209-362: finished hypotheses keep extending, no
 length normalisation); the only difference to GPV._beam_device's torch path is the last bit of lp (torch forms x - m - log s).
 Caller conditions: 1 <= K <= MAX_K, K <= V, T <= MAX_T; a mask leaves at least K finite entries per row; a NaN logit gives an undefined
@@ -50,6 +52,26 @@ def check_extents(K, V, T, t=None):
         raise ValueError(f'beam: step {t} outside 0 .. {T - 2}')
 
 
+def select_slots(out, b, cands, seqs, t, inv_pen=None, default=None):
+    """Steps 5-7 for batch element b.  cands: the candidates in k1*K + k2 order, each a dict of k1, w and what the slot takes under
+    the names of `out`: seq_lp (the score), length (len') and the search's own state words.  default: the candidate (k1 = 0) that the
+    slots behind the last candidate take.  Writes out[...][b, k], out['seqs'][k, b] and out['tok'][k*B + b]."""
+    K, B, T = seqs.shape
+
+    def key(c):
+        pen = None if inv_pen is None else F32(inv_pen[min(max(int(c['length']), 0), T)])
+        return c['seq_lp'] if pen is None else F32(c['seq_lp'] * pen)            # one fp32 multiply
+    chosen = sorted(cands, key=lambda c: -float(key(c)))[:K]                     # stable; float(fp32) is exact, so is its negation
+    for k, c in enumerate(chosen + [default] * (K - len(chosen))):
+        out['parent'][b, k] = c['k1']
+        out['seqs'][k, b, :t] = seqs[c['k1'], b, :t]
+        out['seqs'][k, b, t] = c['w']
+        out['tok'][k * B + b] = c['w']
+        for name, v in c.items():
+            if name not in ('k1', 'w'):
+                out[name][b, k] = v
+
+
 def beam_step_host(logits, lse, seq_lp, seqs, finished, length, t, mode, pad_id, stop_id, inv_pen=None, vocab_mask=None):
     """One step.  logits [K*B, V] (values exactly representable in fp32: fp32 or widened bf16), lse [K*B] fp32 (the device's, or any
     log-sum-exp of the masked rows), seq_lp [B,K] fp32, seqs [K,B,T] int64, finished [B,K] 0/1, length [B,K] int.  Nothing is modified.
@@ -70,12 +92,11 @@ def beam_step_host(logits, lse, seq_lp, seqs, finished, length, t, mode, pad_id,
     out = {'parent': np.zeros((B, K), np.int32), 'tok': np.zeros(K * B, np.int64), 'seqs': np.array(seqs, dtype=np.int64),
            'seq_lp': np.zeros((B, K), F32), 'finished': np.zeros((B, K), np.int32), 'length': np.zeros((B, K), np.int32)}
     for b in range(B):
-        cands = []                                                               # (key, k1*K + k2, k1, w, score, len')
+        cands = []                                                               # in k1*K + k2 order
         for k1 in range(K):
             r = k1 * B + b
             fin = bool(finished[b, k1])
             ln = int(length[b, k1]) + (0 if fin else 1)
-            pen = None if inv_pen is None else F32(inv_pen[min(max(ln, 0), T)])
             for k2 in range(K):
                 if mode == FREEZE and fin:
                     if k2 > 0:
@@ -87,17 +108,9 @@ def beam_step_host(logits, lse, seq_lp, seqs, finished, length, t, mode, pad_id,
                     score = F32(seq_lp[b, k1] + lp)                              # one fp32 add
                     if t == 0 and k1 > 0:
                         score = F32(-1e9)
-                key = score if pen is None else F32(score * pen)                 # one fp32 multiply
-                cands.append((key, k1 * K + k2, k1, w, score, ln))
-        cands.sort(key=lambda c: (-float(c[0]), c[1]))                           # step 6 (float(fp32) is exact, so is its negation)
-        for k, (_, _, k1, w, score, ln) in enumerate(cands[:K]):
-            out['parent'][b, k] = k1
-            out['seq_lp'][b, k] = score
-            out['seqs'][k, b, :t] = seqs[k1, b, :t]
-            out['seqs'][k, b, t] = w
-            out['tok'][k * B + b] = w
-            out['finished'][b, k] = int(mode == FREEZE and (bool(finished[b, k1]) or w == stop_id))
-            out['length'][b, k] = ln
+                cands.append({'k1': k1, 'w': w, 'seq_lp': score, 'length': ln,
+                              'finished': int(mode == FREEZE and (fin or w == stop_id))})
+        select_slots(out, b, cands, seqs, t, inv_pen)                            # steps 5-7
     return out
 
 

@@ -639,26 +639,12 @@ class GPV(nn.Module):
         """device part of the phrase-constrained search: outputs dict + '_beam_seqs' [K,B,T] + '_beam_lp' [B,K] + '_beam_phrase' [B,K] int32:
         per token the decoder core, gpv_phrase_step (writes the next tokens straight into kv.tok) and gpv_beam_reorder -- two launches
         beside the decoder's, no allocation inside the loop"""
-        from . import beam as rule, hip_phrase
-        from .decode import GreedyKVDecoder
-        graphed = isinstance(queries, (tuple, list)) and len(queries) == 2 and all(torch.is_tensor(q) for q in queries) and \
-            hasattr(images, 'tensors') and images.tensors.is_cuda and torch.cuda.is_current_stream_capturing()
-        outputs, memory = self._encode(images, queries, self._bert_fork(images, queries) if graphed else None)
+        from . import hip_phrase
+        outputs, memory = self._encode(images, queries, self._bert_fork(images, queries) if self._capturing(images, queries) else None)
         B, K, T = memory.shape[0], beam_size, self.cfg.max_text_len
         dev = memory.device
-        memK = memory.repeat(K, 1, 1)
-        key = (K * B, memK.shape[1], str(dev), RT.dtype, 'beam')
-        kv = self._kvdec.get(key)
-        if kv is None:
-            kv = self._kvdec[key] = GreedyKVDecoder(self, K * B, memK.shape[1], use_graphs=False)
-        kv.memory.copy_(memK.reshape(K * B * memK.shape[1], -1))
-        kv._prepare()
-        inv_pen = None
-        if alpha != 0.0:
-            tables = self.__dict__.setdefault('_beam_tables', {})            # (filled by the warm-up runs: a capture finds it on the device)
-            inv_pen = tables.get((T, alpha, str(dev)))
-            if inv_pen is None:
-                inv_pen = tables[(T, alpha, str(dev))] = torch.from_numpy(rule.length_table(T, alpha)).to(dev)
+        kv = self._beam_kv(memory, K)
+        inv_pen = self._inv_pen(T, alpha, dev)
         pset.device_arrays(dev)                                              # (made once per device, by the warm-up runs of a capture)
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
         seq_lp = torch.zeros(B, K, device=dev)
@@ -666,37 +652,65 @@ class GPV(nn.Module):
         lse = torch.zeros(K * B, device=dev)
         parent, node, length = i32(B, K), i32(B, K), i32(B, K)
         phrase = torch.full((B, K), -1, dtype=torch.int32, device=dev)
-        kv.tok.fill_(self.word_to_idx['__cls__'])
-        for t in range(T - 1):
-            hip_phrase.step(kv._step_core(t), lse, seq_lp, seqs, kv.tok, parent, node, phrase, length, t, pset, inv_pen=inv_pen)
-            if t + 1 < T - 1:                                                  # (nothing reads the caches after the last step)
-                kv.reorder_device(parent, t + 1)
+        self._device_steps(kv, T, parent, lambda t, logits: hip_phrase.step(logits, lse, seq_lp, seqs, kv.tok, parent, node, phrase,
+                                                                            length, t, pset, inv_pen=inv_pen))
         outputs['_beam_seqs'], outputs['_beam_lp'], outputs['_beam_phrase'] = seqs, seq_lp, phrase
         outputs['beam_lengths'], outputs['_phrase_set'] = length, pset
         return outputs
 
+    def _capturing(self, images, queries):
+        """is this call being captured into a graph (device tensors in, a capturing stream)"""
+        return isinstance(queries, (tuple, list)) and len(queries) == 2 and all(torch.is_tensor(q) for q in queries) and \
+            hasattr(images, 'tensors') and images.tensors.is_cuda and torch.cuda.is_current_stream_capturing()
+
+    def _beam_kv(self, memory, K):
+        """the KV-cached decoder (decode.py) of K beams per sample, filled from `memory` repeated K times: all K beams in ONE decoder pass"""
+        from .decode import GreedyKVDecoder
+        memK = memory.repeat(K, 1, 1)
+        R = memK.shape[0]
+        key = (R, memK.shape[1], str(memory.device), RT.dtype, 'beam')
+        kv = self._kvdec.get(key)
+        if kv is None:
+            kv = self._kvdec[key] = GreedyKVDecoder(self, R, memK.shape[1], use_graphs=False)
+        kv.memory.copy_(memK.reshape(R * memK.shape[1], -1))
+        kv._prepare()
+        return kv
+
+    def _inv_pen(self, T, alpha, dev):
+        """the length-penalty table of beam.length_table on the device, made once per (T, alpha, device); None without a penalty"""
+        if alpha == 0.0:
+            return None
+        from . import beam as rule
+        tables = self.__dict__.setdefault('_beam_tables', {})                # (filled by the warm-up runs: a capture finds it on the device)
+        inv_pen = tables.get((T, alpha, str(dev)))
+        if inv_pen is None:
+            inv_pen = tables[(T, alpha, str(dev))] = torch.from_numpy(rule.length_table(T, alpha)).to(dev)
+        return inv_pen
+
+    def _device_steps(self, kv, T, parent, step):
+        """the T - 1 steps of a device search: the decoder core, step(t, logits) (one launch; writes the next tokens straight into kv.tok
+        and the slots' parents into `parent`) and gpv_beam_reorder -- two launches per token beside the decoder's, no allocation"""
+        kv.tok.fill_(self.word_to_idx['__cls__'])
+        for t in range(T - 1):
+            step(t, kv._step_core(t))
+            if t + 1 < T - 1:                                                  # (nothing reads the caches after the last step)
+                kv.reorder_device(parent, t + 1)
+
     def _beam_device(self, images, queries, beam_size, vocab_mask=None, impl='torch', finished='extend', alpha=0.0):
         """device part of the beam search: outputs dict + '_beam_seqs' [K,B,T] + '_beam_lp' [B,K] (no host round trip)"""
-        graphed = isinstance(queries, (tuple, list)) and len(queries) == 2 and all(torch.is_tensor(q) for q in queries) and \
-            hasattr(images, 'tensors') and images.tensors.is_cuda and torch.cuda.is_current_stream_capturing()
-        outputs, memory = self._encode(images, queries, self._bert_fork(images, queries) if graphed else None)
+        outputs, memory = self._encode(images, queries, self._bert_fork(images, queries) if self._capturing(images, queries) else None)
         B, K, T = memory.shape[0], beam_size, self.cfg.max_text_len
         dev = memory.device
         tok = torch.full((K, B, 1), self.word_to_idx['__cls__'], dtype=torch.long, device=dev)
         seq_lp = torch.zeros(B, K, device=dev)
         seqs = torch.zeros(K, B, T, dtype=torch.long, device=dev)
-        memK = memory.repeat(K, 1, 1)                                              # all K beams in ONE decoder pass
         kv = None
         if not self.training and not torch.is_grad_enabled() and self.cfg.get('kv_decode', True):
             # KV-cached decode step (decode.py) instead of the reference's full-prefix pass per token: the decoder is
             # causal, so the logits of the newest position are the same; the caches follow the beams (reorder below)
-            from .decode import GreedyKVDecoder
-            key = (K * B, memK.shape[1], str(dev), RT.dtype, 'beam')
-            kv = self._kvdec.get(key)
-            if kv is None:
-                kv = self._kvdec[key] = GreedyKVDecoder(self, K * B, memK.shape[1], use_graphs=False)
-            kv.memory.copy_(memK.reshape(K * B * memK.shape[1], -1))
-            kv._prepare()
+            kv = self._beam_kv(memory, K)
+        else:
+            memK = memory.repeat(K, 1, 1)                                          # all K beams in ONE decoder pass
         if impl == 'device':
             if kv is None:
                 raise RuntimeError("forward_beam_search: impl='device' needs the KV-cached decoder (eval mode, no grad, cfg kv_decode); "
@@ -729,17 +743,11 @@ class GPV(nn.Module):
         return outputs
 
     def _beam_steps_device(self, outputs, kv, B, K, T, vocab_mask, finished, alpha):
-        """the T - 1 steps of the device path: decoder core, gpv_beam_step (writes the next tokens straight into kv.tok), gpv_beam_reorder
-        -- two launches per token beside the decoder's, no allocation inside the loop"""
+        """the device path of the plain search: _device_steps with gpv_beam_step"""
         from . import beam as rule, hip_beam
         rule.check_extents(K, len(self.vocab), T)
         dev = kv.tok.device
-        inv_pen = None
-        if alpha != 0.0:
-            tables = self.__dict__.setdefault('_beam_tables', {})            # (filled by the warm-up runs: a capture finds it on the device)
-            inv_pen = tables.get((T, alpha, str(dev)))
-            if inv_pen is None:
-                inv_pen = tables[(T, alpha, str(dev))] = torch.from_numpy(rule.length_table(T, alpha)).to(dev)
+        inv_pen = self._inv_pen(T, alpha, dev)
         if vocab_mask is not None:
             vocab_mask = vocab_mask.to(device=dev, dtype=torch.float32).contiguous()
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
@@ -747,13 +755,9 @@ class GPV(nn.Module):
         seqs = torch.zeros(K, B, T, dtype=torch.long, device=dev)
         lse = torch.zeros(K * B, device=dev)
         parent, fin, length = i32(B, K), i32(B, K), i32(B, K)
-        kv.tok.fill_(self.word_to_idx['__cls__'])
         mode, pad, stop = rule.MODES[finished], self.word_to_idx['__pad__'], self.word_to_idx['__stop__']
-        for t in range(T - 1):
-            hip_beam.step(kv._step_core(t), lse, seq_lp, seqs, kv.tok, parent, fin, length, t, mode, pad, stop,
-                          inv_pen=inv_pen, vocab_mask=vocab_mask)
-            if t + 1 < T - 1:                                                  # (nothing reads the caches after the last step)
-                kv.reorder_device(parent, t + 1)
+        self._device_steps(kv, T, parent, lambda t, logits: hip_beam.step(logits, lse, seq_lp, seqs, kv.tok, parent, fin, length, t, mode,
+                                                                          pad, stop, inv_pen=inv_pen, vocab_mask=vocab_mask))
         outputs['_beam_seqs'], outputs['_beam_lp'] = seqs, seq_lp
         outputs['beam_lengths'], outputs['beam_finished'] = length, fin
         return outputs

@@ -42,35 +42,44 @@ def lib():
     return _LIB
 
 
+def step_fields(module, logits, lse, seq_lp, seqs, tok, parent, length, inv_pen, extents):
+    """What gpv_beam_step and gpv_phrase_step take alike, checked and packed once: -> (fields of the argument struct, K, B, T, V).
+    module names the binding in the messages ('hip_beam' / 'hip_phrase'); extents(K, V, T) is its rule's own check of the shapes."""
+    want = partial(_native.want, module)
+    if not logits.is_cuda:
+        raise RuntimeError(f'gpv1_amd: {module}: logits must live on the GPU (no CPU fallback exists for the device '
+                           f'{module[4:]} step)')
+    if logits.dim() != 2 or seqs.dim() != 3:
+        raise ValueError(f'{module}.step: logits must be [K*B, V] and seqs [K,B,T], got {tuple(logits.shape)} {tuple(seqs.shape)}')
+    K, B, T = seqs.shape
+    R, V = logits.shape
+    extents(K, V, T)
+    if R != K * B:
+        raise ValueError(f'{module}.step: logits must have K*B = {K * B} rows, got {R}')
+    if logits.dtype not in _DTYPES:
+        raise ValueError(f'{module}.step: logits must be bfloat16 or float32, got {logits.dtype}')
+    if logits.stride(1) != 1 or (R > 1 and logits.stride(0) < V):
+        raise ValueError(f'{module}.step: logits need unit column stride and a row pitch >= V, got strides {tuple(logits.stride())}')
+    return dict(logits=logits.data_ptr(), pitch=logits.stride(0) if R > 1 else V,
+                inv_pen=None if inv_pen is None else want('inv_pen', inv_pen, torch.float32, (T + 1,)),
+                lse=want('lse', lse, torch.float32, (R,)), seq_lp=want('seq_lp', seq_lp, torch.float32, (B, K)),
+                seqs=want('seqs', seqs, torch.int64, (K, B, T)), tok=want('tok', tok, torch.int64, (R,)),
+                parent=want('parent', parent, torch.int32, (B, K)), length=want('length', length, torch.int32, (B, K)),
+                B=B, K=K, V=V, T=T, dtype=_DTYPES[logits.dtype]), K, B, T, V
+
+
 def step(logits, lse, seq_lp, seqs, tok, parent, finished, length, t, mode, pad_id, stop_id, inv_pen=None, vocab_mask=None):
     """gpv_beam_step on the current stream: one launch, no sync, everything in place.  logits [K*B, V] bf16 / fp32 with unit column
     stride (any row pitch >= V: a view of the decoder's [K*B, T, V] buffer), lse [K*B] fp32 out, seq_lp [B,K] fp32, seqs [K,B,T] int64,
     tok [K*B] int64 out, parent [B,K] int32 out, finished / length [B,K] int32; inv_pen [T+1] fp32 or None, vocab_mask [V] fp32 or None."""
-    if not logits.is_cuda:
-        raise RuntimeError('gpv1_amd: hip_beam: logits must live on the GPU (no CPU fallback exists for the device beam step)')
-    if logits.dim() != 2 or seqs.dim() != 3:
-        raise ValueError(f'hip_beam.step: logits must be [K*B, V] and seqs [K,B,T], got {tuple(logits.shape)} {tuple(seqs.shape)}')
-    K, B, T = seqs.shape
-    R, V = logits.shape
-    rule.check_extents(K, V, T, t)
-    if R != K * B:
-        raise ValueError(f'hip_beam.step: logits must have K*B = {K * B} rows, got {R}')
-    if logits.dtype not in _DTYPES:
-        raise ValueError(f'hip_beam.step: logits must be bfloat16 or float32, got {logits.dtype}')
-    if logits.stride(1) != 1 or (R > 1 and logits.stride(0) < V):
-        raise ValueError(f'hip_beam.step: logits need unit column stride and a row pitch >= V, got strides {tuple(logits.stride())}')
+    f, K, B, T, V = step_fields('hip_beam', logits, lse, seq_lp, seqs, tok, parent, length, inv_pen,
+                                lambda K, V, T: rule.check_extents(K, V, T, t))
     if mode not in (rule.EXTEND, rule.FREEZE):
         raise ValueError(f'hip_beam.step: mode must be EXTEND (0) or FREEZE (1), got {mode!r}')
     if not (0 <= pad_id < V and 0 <= stop_id < V):
         raise ValueError(f'hip_beam.step: pad_id / stop_id must lie in the vocabulary, got {pad_id} / {stop_id} of {V}')
-    a = BeamArgs(logits=logits.data_ptr(), pitch=logits.stride(0) if R > 1 else V,
-                 vocab_mask=None if vocab_mask is None else _want('vocab_mask', vocab_mask, torch.float32, (V,)),
-                 inv_pen=None if inv_pen is None else _want('inv_pen', inv_pen, torch.float32, (T + 1,)),
-                 lse=_want('lse', lse, torch.float32, (R,)), seq_lp=_want('seq_lp', seq_lp, torch.float32, (B, K)),
-                 seqs=_want('seqs', seqs, torch.int64, (K, B, T)), tok=_want('tok', tok, torch.int64, (R,)),
-                 parent=_want('parent', parent, torch.int32, (B, K)), finished=_want('finished', finished, torch.int32, (B, K)),
-                 length=_want('length', length, torch.int32, (B, K)), B=B, K=K, V=V, T=T, t=t, mode=mode, pad_id=pad_id,
-                 stop_id=stop_id, dtype=_DTYPES[logits.dtype])
+    a = BeamArgs(vocab_mask=None if vocab_mask is None else _want('vocab_mask', vocab_mask, torch.float32, (V,)),
+                 finished=_want('finished', finished, torch.int32, (B, K)), t=t, mode=mode, pad_id=pad_id, stop_id=stop_id, **f)
     _chk(lib().gpv_beam_step(C.byref(a), _stream()), 'gpv_beam_step')
 
 

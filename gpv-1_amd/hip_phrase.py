@@ -8,14 +8,13 @@ from functools import partial
 
 import torch
 
-from . import _native
+from . import _native, hip_beam
 from . import phrases as rule
 from .hip import _chk, _stream
 
 EXPORTS = ['gpv_phrase_step']
 MAX_K, MAX_T = rule.MAX_K, rule.MAX_T                     # GPV_PHRASE_MAX_K, GPV_PHRASE_MAX_T
 DONE, VOID = rule.DONE, rule.VOID                         # GPV_PHRASE_DONE, GPV_PHRASE_VOID
-_DTYPES = {torch.bfloat16: 0, torch.float32: 1}           # GPV_PHRASE_BF16, GPV_PHRASE_F32
 _LIB = None
 _LIB_PATH = _native.lib_path('phrase')
 _want = partial(_native.want, 'hip_phrase')
@@ -43,30 +42,15 @@ def step(logits, lse, seq_lp, seqs, tok, parent, node, phrase, length, t, pset, 
     """gpv_phrase_step on the current stream: one launch, no sync, everything in place.  logits [K*B, V] bf16 / fp32 with unit column
     stride (any row pitch >= V: a view of the decoder's [K*B, T, V] buffer), lse [K*B] fp32 out, seq_lp [B,K] fp32, seqs [K,B,T] int64,
     tok [K*B] int64 out, parent [B,K] int32 out, node / phrase / length [B,K] int32; pset a phrases.PhraseSet; inv_pen [T+1] fp32 or None."""
-    if not logits.is_cuda:
-        raise RuntimeError('gpv1_amd: hip_phrase: logits must live on the GPU (no CPU fallback exists for the device phrase step)')
-    if logits.dim() != 2 or seqs.dim() != 3:
-        raise ValueError(f'hip_phrase.step: logits must be [K*B, V] and seqs [K,B,T], got {tuple(logits.shape)} {tuple(seqs.shape)}')
-    K, B, T = seqs.shape
-    R, V = logits.shape
-    rule.check_extents(K, T, pset, t)
-    if R != K * B:
-        raise ValueError(f'hip_phrase.step: logits must have K*B = {K * B} rows, got {R}')
-    if V != pset.V:
-        raise ValueError(f'hip_phrase.step: the phrase set was compiled for a vocabulary of {pset.V}, the logits have {V} columns')
-    if logits.dtype not in _DTYPES:
-        raise ValueError(f'hip_phrase.step: logits must be bfloat16 or float32, got {logits.dtype}')
-    if logits.stride(1) != 1 or (R > 1 and logits.stride(0) < V):
-        raise ValueError(f'hip_phrase.step: logits need unit column stride and a row pitch >= V, got strides {tuple(logits.stride())}')
+    def extents(K, V, T):
+        rule.check_extents(K, T, pset, t)
+        if V != pset.V:
+            raise ValueError(f'hip_phrase.step: the phrase set was compiled for a vocabulary of {pset.V}, the logits have {V} columns')
+    f, K, B, T, V = hip_beam.step_fields('hip_phrase', logits, lse, seq_lp, seqs, tok, parent, length, inv_pen, extents)
     off, ctok, cnode, term = pset.device_arrays(logits.device)
     M, E = pset.M, pset.E
-    a = PhraseArgs(logits=logits.data_ptr(), pitch=logits.stride(0) if R > 1 else V,
-                   inv_pen=None if inv_pen is None else _want('inv_pen', inv_pen, torch.float32, (T + 1,)),
-                   lse=_want('lse', lse, torch.float32, (R,)), seq_lp=_want('seq_lp', seq_lp, torch.float32, (B, K)),
-                   seqs=_want('seqs', seqs, torch.int64, (K, B, T)), tok=_want('tok', tok, torch.int64, (R,)),
-                   parent=_want('parent', parent, torch.int32, (B, K)), length=_want('length', length, torch.int32, (B, K)),
-                   node=_want('node', node, torch.int32, (B, K)), phrase=_want('phrase', phrase, torch.int32, (B, K)),
+    a = PhraseArgs(node=_want('node', node, torch.int32, (B, K)), phrase=_want('phrase', phrase, torch.int32, (B, K)),
                    child_off=_want('child_off', off, torch.int32, (M + 1,)), child_tok=_want('child_tok', ctok, torch.int32, (E,)),
                    child_node=_want('child_node', cnode, torch.int32, (E,)), terminal=_want('terminal', term, torch.int32, (M,)),
-                   B=B, K=K, V=V, T=T, t=t, pad_id=pset.pad_id, stop_id=pset.stop_id, dtype=_DTYPES[logits.dtype], M=M, E=E)
+                   t=t, pad_id=pset.pad_id, stop_id=pset.stop_id, M=M, E=E, **f)
     _chk(lib().gpv_phrase_step(C.byref(a), _stream()), 'gpv_phrase_step')

@@ -22,11 +22,9 @@ THE RULE.  Step t (0 <= t < T-1), batch element b, parent k1 = 0..K-1, logits ro
     other v: node' = that child, phrase' = -1.
  3. DONE parent: exactly one candidate, k2 = 0: token pad_id, score and length unchanged, node' = DONE, phrase' carried.
  4. VOID parent: no candidate.  t == 0: a parent k1 > 0 has no candidate (all slots start at the root; only slot 0 counts).
- 5. key = score * inv_pen[clamp(len', 0, T)]: one fp32 multiply; inv_pen None: key = score.  The table is beam.length_table.
- 6. Selection: the first K candidates by key descending, ties to the lower k1*K + k2.  With only c < K candidates the slots c..K-1
-    become VOID: parent 0, token pad_id, seq_lp = -1e9 exactly, node' = VOID, phrase' = -1, length' = 0.
- 7. Slot k with the chosen (k1, k2, w) (a VOID slot: (0, -, pad_id)): parent[b,k] = k1; seq_lp' = the raw score;
-    seqs'[k,b,:t] = seqs[k1,b,:t], seqs'[k,b,t] = w (positions behind t are left alone); tok[k*B+b] = w; node', phrase', length'.
+ 5-7. Key, selection and slot write are steps 5-7 of gpv1_amd.beam (beam.select_slots), the search's own state being node' and
+    phrase'.  With only c < K candidates the slots c..K-1 become VOID: parent 0, token pad_id, seq_lp = -1e9 exactly, node' = VOID,
+    phrase' = -1, length' = 0.
 Caller conditions: 1 <= K <= 8, 2 <= T <= 64, pset.max_len <= T - 2 (so __stop__ always fits).  Slots come out best first; the finished
 slots of one batch element name pairwise different phrases (trie paths are unique).
 """
@@ -153,11 +151,12 @@ def phrase_step_host(logits, lse, seq_lp, seqs, node, phrase, length, t, pad_id,
         raise ValueError(f'phrases: pad_id / stop_id {pad_id} / {stop_id} are not the set\'s ({pset.pad_id} / {pset.stop_id})')
     lse = np.asarray(lse, dtype=F32)
     seq_lp = np.asarray(seq_lp, dtype=F32)
-    out = {'parent': np.zeros((B, K), np.int32), 'tok': np.full(K * B, pad_id, np.int64), 'seqs': np.array(seqs, dtype=np.int64),
-           'seq_lp': np.full((B, K), VOID_LP, F32), 'node': np.full((B, K), VOID, np.int32), 'phrase': np.full((B, K), -1, np.int32),
+    out = {'parent': np.zeros((B, K), np.int32), 'tok': np.zeros(K * B, np.int64), 'seqs': np.array(seqs, dtype=np.int64),
+           'seq_lp': np.zeros((B, K), F32), 'node': np.zeros((B, K), np.int32), 'phrase': np.zeros((B, K), np.int32),
            'length': np.zeros((B, K), np.int32)}
+    void = {'k1': 0, 'w': pad_id, 'seq_lp': VOID_LP, 'length': 0, 'node': VOID, 'phrase': -1}
     for b in range(B):
-        cands = []                                                   # (key, k1*K + k2, k1, w, score, len', node', phrase')
+        cands = []                                                   # in k1*K + k2 order
         for k1 in range(K):
             r = k1 * B + b
             n = int(node[b, k1])
@@ -171,20 +170,8 @@ def phrase_step_host(logits, lse, seq_lp, seqs, node, phrase, length, t, pad_id,
                 for w, n2, p2 in al:
                     lp = F32(x[r, w] - lse[r])                       # one fp32 subtract
                     found.append((w, F32(seq_lp[b, k1] + lp), int(length[b, k1]) + 1, n2, p2))     # one fp32 add
-            for k2, (w, score, ln, n2, p2) in enumerate(found):
-                key = score if inv_pen is None else F32(score * F32(inv_pen[min(max(ln, 0), T)]))  # one fp32 multiply
-                cands.append((key, k1 * K + k2, k1, w, score, ln, n2, p2))
-        cands.sort(key=lambda c: (-float(c[0]), c[1]))
-        cands = cands[:K]
-        for k in range(K):
-            k1, w = (cands[k][2], cands[k][3]) if k < len(cands) else (0, pad_id)
-            out['parent'][b, k] = k1
-            out['seqs'][k, b, :t] = seqs[k1, b, :t]
-            out['seqs'][k, b, t] = w
-            out['tok'][k * B + b] = w
-            if k < len(cands):
-                _, _, _, _, score, ln, n2, p2 = cands[k]
-                out['seq_lp'][b, k], out['length'][b, k], out['node'][b, k], out['phrase'][b, k] = score, ln, n2, p2
+            cands += [{'k1': k1, 'w': w, 'seq_lp': score, 'length': ln, 'node': n2, 'phrase': p2} for w, score, ln, n2, p2 in found]
+        _beam.select_slots(out, b, cands, seqs, t, inv_pen, default=void)   # steps 5-7
     return out
 
 

@@ -2,8 +2,7 @@
  * byte what the host rule writes (gpv1_amd.jpeg_encode.encode_host in numpy, gpv-1_amd/csrc/jpeg_enc_host.h in plain C++), which in
  * turn is the file Pillow writes for the same pixels.  DESIGN.md section 6h states the rule.
  *
- * An EXTENSION library: it is built by the Makefile's `extensions` target and listed in gpv1_amd._native.EXTENSIONS, beside the seven
- * libraries of `all` / LIBRARIES, whose number is pinned.  gpv_enc_header is HOST code (no HIP call); the other two follow the rules
+ * A library of its own, listed in gpv1_amd._native.LIBRARIES and built by the Makefile's `all` like the others.  gpv_enc_header is HOST code (no HIP call); the other two follow the rules
  * of the device libraries: a hipError_t as int (0 = ok), launches on `stream`, never synchronise, allocate nothing, keep no global
  * state.  Anything outside the stated extents returns hipErrorInvalidValue (1) before a launch.
  *

@@ -1,6 +1,7 @@
 """C-ABI checks that need no GPU, for every native library of gpv1_amd._native.LIBRARIES: it loads, exports exactly the entry points
 its public header declares and its binding module lists, the ctypes mirrors have the C layout (sizes and field offsets, via a
-gcc-compiled probe), the argtypes are the header's prototypes and the constants of gpv-1_amd/hip.py are the header's.
+gcc-compiled probe), the argtypes are the header's prototypes, the constants of gpv-1_amd/hip.py are the header's, and the Makefile
+builds exactly the table's libraries, each from its own sources with its own flags.
 
 A new library adds rows to PINNED, SIGNATURES and (if it has structs) STRUCTS below; the test bodies stay as they are."""
 import ctypes
@@ -22,20 +23,26 @@ PINNED = {'hip': 52,
           'match': ['gpv_match_boxes', 'gpv_match_lsap', 'gpv_match_set_loss'],
           'health': ['gpv_health_commit', 'gpv_health_stats'],
           'beam': ['gpv_beam_reorder', 'gpv_beam_step'],
-          'huff': ['gpv_huff_decode', 'gpv_huff_prepare', 'gpv_huff_workspace_bytes']}
-NO_GETENV = ('hip', 'huff')          # libraries that must not read the environment
+          'huff': ['gpv_huff_decode', 'gpv_huff_prepare', 'gpv_huff_workspace_bytes'],
+          'enc': ['gpv_enc_encode', 'gpv_enc_header', 'gpv_enc_workspace_bytes'],
+          'phrase': ['gpv_phrase_step']}
+NO_GETENV = ('hip', 'huff', 'enc', 'phrase')          # libraries that must not read the environment
+FP_CONTRACT_OFF = ('eval', 'cap', 'match', 'health', 'beam', 'enc', 'phrase')      # compiled with -ffp-contract=off: a host rule rounds every operation
 # C struct -> its ctypes mirror in the binding module
 STRUCTS = {'hip': {'gpv_gemm_args': 'GemmArgs', 'gpv_conv_args': 'ConvArgs', 'gpv_attn_args': 'AttnArgs', 'gpv_tt_problem': 'TTProblem',
                    'gpv_fold_problem': 'FoldProblem', 'gpv_tc_problem': 'TCProblem', 'gpv_image_desc': 'ImageDesc',
                    'gpv_conv_wgrad_problem': 'ConvWgradProblem', 'gpv_jpeg_info': 'JpegInfo', 'gpv_jpeg_desc': 'JpegDesc'},
            'beam': {'gpv_beam_args': 'BeamArgs', 'gpv_beam_reorder_args': 'ReorderArgs'},
-           'huff': {'gpv_huff_table': 'HuffTable', 'gpv_huff_desc': 'HuffDesc'}}
+           'huff': {'gpv_huff_table': 'HuffTable', 'gpv_huff_desc': 'HuffDesc'},
+           'enc': {'gpv_enc_desc': 'EncDesc'},
+           'phrase': {'gpv_phrase_args': 'PhraseArgs'}}
 # one letter per parameter: P pointer, i int, f float, q int64_t / long long.  The side libraries only: the hot path's entry points
 # carry no argtypes (hip.lib).
 SIGNATURES = {'gpv_match_set_loss': 'PPPPPPPPiiiiiifPPPPPPP', 'gpv_match_boxes': 'PPPPPiiiiiifffPPPPPP', 'gpv_match_lsap': 'PPiiiiPPPPP',
               'gpv_eval_det_ap': 'PPPPiiifPPPPP', 'gpv_cap_scores': 'PPPPPiiiiPPiPPqPPPPPPPP', 'gpv_health_stats': 'PiPiPPP',
               'gpv_health_commit': 'PiiPPPP', 'gpv_huff_prepare': 'PqPPPqPP', 'gpv_huff_workspace_bytes': 'iiqP',
-              'gpv_huff_decode': 'PiiqPqP', 'gpv_beam_step': 'PP', 'gpv_beam_reorder': 'PP'}
+              'gpv_huff_decode': 'PiiqPqP', 'gpv_beam_step': 'PP', 'gpv_beam_reorder': 'PP', 'gpv_enc_workspace_bytes': 'iqP',
+              'gpv_enc_encode': 'PiiiPqPqPPP', 'gpv_enc_header': 'iiiiPP', 'gpv_phrase_step': 'PP'}
 SIDE = [k for k in probe.LIBRARIES if k != 'hip']
 
 
@@ -61,6 +68,34 @@ def test_library_exports_exactly_the_declared_entry_points(key):
             assert not any(n.startswith(other.prefix) for n in names), other.prefix
     if key in NO_GETENV:
         assert not re.search(r'\bgetenv\b', probe.imports(path)), f'{l.file} reads the environment'
+
+
+def _make(*args):
+    csrc = os.path.join(ROOT, 'gpv-1_amd', 'csrc')
+    return subprocess.run(['make', '-n', '-C', csrc] + list(args), capture_output=True, text=True, check=True).stdout
+
+
+@pytest.mark.parametrize('key', list(probe.LIBRARIES))
+def test_makefile_builds_the_library_from_its_own_sources(key):
+    """what the Makefile builds, not what it says: a dry run of `all` links exactly the files of LIBRARIES, this one from the objects of
+    its own sources, each compiled for gfx950 and with -ffp-contract=off exactly where a host rule is repeated bit for bit; `clean`
+    names every library and object"""
+    import __graft_entry__ as entry
+    dry = _make('-B', 'all').splitlines()
+    links = {l.split()[-1]: l.split() for l in dry if ' -shared ' in l}
+    assert sorted(links) == sorted(l.file for l in probe.LIBRARIES.values())
+    objs = [os.path.basename(s)[:-4] + '.o' for s in entry._make_lists(key)[0]]
+    line = links[probe.LIBRARIES[key].file]
+    assert [w for w in line if w.endswith('.o') and w != 'build_id.o'] == objs
+    assert ('build_id.o' in line) == (key == 'hip')
+    others = {o for k in probe.LIBRARIES if k != key for o in (os.path.basename(s)[:-4] + '.o' for s in entry._make_lists(k)[0])}
+    assert not others & set(objs)
+    for o in objs:
+        compile_line = [l for l in dry if f' -c {o[:-2]}.hip ' in l]
+        assert len(compile_line) == 1 and '--offload-arch=gfx950' in compile_line[0].split()
+        assert ('-ffp-contract=off' in compile_line[0].split()) == (key in FP_CONTRACT_OFF), compile_line[0]
+    clean = _make('clean').split()
+    assert set(links) <= set(clean) and set(objs) <= set(clean)
 
 
 def test_abi_version_is_one_number():

@@ -1,101 +1,27 @@
-"""C-ABI checks of the extension library libgpv_enc.so that need no GPU: what tests/test_abi_cpu.py checks for the seven libraries
-of gpv1_amd._native.LIBRARIES (exports == header == binding, prototypes, struct layout, no environment reads), that the seven stay
-seven, that the Makefile builds the extension by a target of its own, the header's constants, and the refusal of bad extents."""
+"""C-ABI checks of libgpv_enc.so that need no GPU and are its own: the header's constants, the size the workspace formula counts on,
+the host-only header entry point and the refusal of bad extents.  (Exports, prototypes, struct layout, Makefile: tests/test_abi_cpu.py.)"""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
-import __graft_entry__ as entry
 from gpv1_amd import _native
 from tests import abi_probe as probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEY = 'enc'
-PINNED = ['gpv_enc_encode', 'gpv_enc_header', 'gpv_enc_workspace_bytes']
-STRUCTS = {'gpv_enc_desc': 'EncDesc'}
-SIGNATURES = {'gpv_enc_workspace_bytes': 'iqP', 'gpv_enc_encode': 'PiiiPqPqPPP', 'gpv_enc_header': 'iiiiPP'}
 
 
 def module():
-    import importlib
-    return importlib.import_module(_native.module_name(KEY))
+    return probe.module(KEY)
 
 
 def built():
-    if not os.path.exists(module()._LIB_PATH):
-        entry.build()
-    return module()._LIB_PATH
-
-
-def test_the_seven_libraries_stay_seven_and_the_extension_has_a_table_of_its_own():
-    assert len(_native.LIBRARIES) == 7 and KEY not in _native.LIBRARIES
-    assert list(_native.EXTENSIONS) == [KEY]
-    l = _native.EXTENSIONS[KEY]
-    assert (l.file, l.header, l.prefix) == ('libgpv_enc.so', 'gpv_enc.h', 'gpv_enc_')
-    assert _native.module_name(KEY) == 'gpv1_amd.hip_enc'
-    assert _native.lib_path(KEY).endswith('gpv-1_amd/csrc/libgpv_enc.so') and _native.header_path(KEY).endswith('include/gpv_enc.h')
-    assert _native.lib_path('huff').endswith('libgpv_huff.so')                # the loader still finds the seven
-
-
-def test_makefile_links_the_extension_by_its_own_target():
-    csrc = os.path.join(ROOT, 'gpv-1_amd', 'csrc')
-    def links(target):
-        dry = subprocess.run(['make', '-n', '-B', '-C', csrc, target], capture_output=True, text=True, check=True).stdout.splitlines()
-        return {l.split()[-1]: l.split() for l in dry if ' -shared ' in l}
-    assert sorted(links('all')) == sorted(l.file for l in _native.LIBRARIES.values()) and len(links('all')) == 7
-    ext = links('extensions')
-    assert list(ext) == ['libgpv_enc.so'] and 'jpeg_enc.o' in ext['libgpv_enc.so']
-    compile_line = [l for l in subprocess.run(['make', '-n', '-B', '-C', csrc, 'extensions'], capture_output=True, text=True, check=True).stdout.splitlines()
-                    if ' -c jpeg_enc.hip' in l]
-    assert len(compile_line) == 1 and '-ffp-contract=off' in compile_line[0] and '--offload-arch=gfx950' in compile_line[0]
-    clean = subprocess.run(['make', '-n', '-C', csrc, 'clean'], capture_output=True, text=True, check=True).stdout.split()
-    assert 'libgpv_enc.so' in clean and 'jpeg_enc.o' in clean
-
-
-def test_library_exports_exactly_the_declared_entry_points():
-    l, mod = _native.EXTENSIONS[KEY], module()
-    names = entry._declared(_native.header_path(KEY), l.prefix)
-    assert names == PINNED == sorted(mod.EXPORTS)
-    path = built()
-    assert entry._exported(path) == names
-    for other in _native.LIBRARIES.values():                 # no entry point of the seven carries this prefix, and none here theirs
-        assert not other.prefix.startswith(l.prefix), other.prefix
-        if other.key != 'hip':
-            assert not any(n.startswith(other.prefix) for n in names), other.prefix
-    hot = entry._declared(_native.header_path('hip'), 'gpv_')
-    assert not any(n.startswith(l.prefix) for n in hot)
-    assert not re.search(r'\bgetenv\b', probe.imports(path)), 'libgpv_enc.so reads the environment'
-
-
-def test_argtypes_are_the_header_prototypes():
-    mod = module()
-    src = entry._header_source(_native.header_path(KEY))
-    protos = {}
-    for name, params in re.findall(r'\bint\s+(gpv_enc_\w+)\s*\(([^)]*)\)\s*;', src):
-        protos[name] = ''.join('P' if '*' in p else probe._C_CLASS[' '.join(p.replace('const ', ' ').split()[:-1])] for p in params.split(','))
-    assert protos == SIGNATURES
-    built()
-    for name, sig in protos.items():
-        fn = getattr(mod.lib(), name)
-        assert fn.restype is ctypes.c_int and probe.argtypes_classes(fn) == sig, name
-
-
-def test_ctypes_structs_match_the_c_layout(tmp_path):
-    mod = module()
-    pairs = [(cname, getattr(mod, mirror)) for cname, mirror in STRUCTS.items()]
-    layout = probe.c_layout(tmp_path, [_native.header_path(KEY)], pairs)
-    for cname, cls in pairs:
-        assert layout[cname] == probe.ctypes_layout(cls), (cname, layout[cname], probe.ctypes_layout(cls))
-    mirrors = {n for n, v in vars(mod).items() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v.__module__ == mod.__name__}
-    assert mirrors == set(STRUCTS.values())
-    assert ctypes.sizeof(mod.EncDesc) == 80                  # the workspace formula of the header counts on it
+    return probe.built(KEY)
 
 
 def test_header_constants_are_the_mirrors():
     mod = module()
+    assert ctypes.sizeof(mod.EncDesc) == 80                  # the workspace formula of the header counts on it
     from gpv1_amd import jpeg_encode as E
     src = open(_native.header_path(KEY)).read()
     const = {k: int(eval(v)) for k, v in re.findall(r'#define (GPV_ENC_\w+) (\([^)]*\)|\d+)', src)}
