@@ -139,7 +139,8 @@ def boxes_to_h5py(npz_path, h5py_path):
 def make_predictions(model, batches, eval_dir, task, subset='val', data_split='original_split', num_eval_batches=None,
                      vocab_mask=None, beam_size=None, beam=None, answer_set=None, classes=COCO_CLASSES):
     """compute_predictions.py:30-85; returns (predictions dict, json path, boxes path).  beam_size / beam (added keys, as in
-    inference.predict: beam.impl, beam.finished, beam.length_penalty): answers by beam search instead of greedy decoding; a vocabulary
+    inference.predict: beam.impl, beam.finished, beam.length_penalty, beam.no_repeat_ngram, beam.min_length,
+    beam.repetition_penalty): answers by beam search instead of greedy decoding; a vocabulary
     mask then needs beam.impl = device (GPV.forward_beam_search).  answer_set (added): None / 'tokens' is the reference's flat
     vocabulary mask, unchanged; 'phrases' answers from the closed set of `classes` (create_phrase_set; GPV.forward_beam_search with
     phrases=, beam_size default 4): every answer written is one of the class names"""

@@ -135,13 +135,14 @@ __device__ __forceinline__ Best pop_best(Shared& sh, int tid, float hv, int hi) 
 
 // lse of one row with maximum m, to lse_s[k1] and *lse_out: the one statement of the order gpv_beam.h pins -- every lane adds
 // expf(x - m) in ascending v, xor butterflies fold a wave, lane 0 adds the four wave sums in wave order (beam.n_chain bounds the chain)
-template <bool BF, bool MASK>
-__device__ __forceinline__ void row_sum_exp(Shared& sh, int tid, const void* row, const float* mask, float m, int V, int k1, float* lse_out) {
+// load(it0, xs): the UN values of the lane from iteration it0 on (load_un, plus whatever the kernel applies to a value on load)
+template <class Load>
+__device__ __forceinline__ void row_sum_exp_of(Shared& sh, int tid, Load load, float m, int V, int k1, float* lse_out) {
   const int iters = (V + LANES - 1) / LANES;
   float s = 0.f;
   for (int it0 = 0; it0 < iters; it0 += UN) {
     float xs[UN];
-    load_un<BF, MASK>(row, mask, it0, tid, V, xs);
+    load(it0, xs);
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const float e = expf(xs[u] - m);
@@ -161,6 +162,11 @@ __device__ __forceinline__ void row_sum_exp(Shared& sh, int tid, const void* row
     *lse_out = lse;
   }
   __syncthreads();
+}
+
+template <bool BF, bool MASK>
+__device__ __forceinline__ void row_sum_exp(Shared& sh, int tid, const void* row, const float* mask, float m, int V, int k1, float* lse_out) {
+  row_sum_exp_of(sh, tid, [&](int it0, float (&xs)[UN]) { load_un<BF, MASK>(row, mask, it0, tid, V, xs); }, m, V, k1, lse_out);
 }
 
 // Thread tid < K*K holds candidate tid = k1*K + k2 (ok: it exists): key = score * inv_pen[len clamped], rank = the number of

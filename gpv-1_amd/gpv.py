@@ -540,8 +540,34 @@ class GPV(nn.Module):
                 raise ValueError("forward_beam_search: a vocabulary mask needs impl='device' (the torch path has none, as the reference)")
         return impl, finished, alpha
 
+    def _beam_constraints(self, beam_size, impl, vocab_mask, phrases, no_repeat_ngram, min_length, repetition_penalty):
+        """the constraints of one call (gpv1_amd.beam, THE CONSTRAINTS): the argument, else cfg['beam'], else off; checked before anything
+        runs -> the keywords of hip_beam.step, {} when all three are off"""
+        from . import beam as rule
+        bc = (self.cfg.get('beam', None) or {}) if phrases is None else {}       # (a phrase search refuses the arguments; the configuration's are not meant for it)
+        given = (no_repeat_ngram, min_length, repetition_penalty)
+        n, m, theta = (bc.get(k, None) if v is None else v for k, v in zip(('no_repeat_ngram', 'min_length', 'repetition_penalty'), given))
+        n, m = int(n or 0), int(m or 0)
+        repetition = rule.rep_factors(theta)
+        V, T = len(self.vocab), self.cfg.max_text_len
+        if not rule.check_constraints(V, T, n, m, repetition):
+            return {}
+        if phrases is not None:
+            raise ValueError('forward_beam_search: phrases and no_repeat_ngram / min_length / repetition_penalty exclude each other (the '
+                             'phrase search is not taught these rules)')
+        if impl == 'torch':
+            raise ValueError("forward_beam_search: no_repeat_ngram / min_length / repetition_penalty need impl='device' (the torch path is "
+                             "the reference's search and is not taught new rules)")
+        # the rule's caller condition: every row keeps K candidates that are finite and not banned (a row bans fewer than T tokens)
+        free = V if vocab_mask is None else int(torch.isfinite(vocab_mask).sum())
+        if free < beam_size + T:
+            raise ValueError(f'forward_beam_search: a constrained search needs at least beam_size + max_text_len = {beam_size + T} '
+                             f'tokens that the vocabulary mask leaves finite, got {free}')
+        return dict(no_repeat_ngram=n, min_length=m, repetition=None if repetition is None else (float(repetition[0]), float(repetition[1])))
+
     @torch.no_grad()
-    def forward_beam_search(self, images, queries, beam_size=1, vocab_mask=None, impl=None, finished=None, length_penalty=None, phrases=None):
+    def forward_beam_search(self, images, queries, beam_size=1, vocab_mask=None, impl=None, finished=None, length_penalty=None, phrases=None,
+                            no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         # (no GPV_OPT_PIPE_SMALL override here: the 320-row GEMMs of beam 5 x batch 64 want the small-M configurations -- 26.0 against 36.8 ms per batch)
         """gpv.py:209-362, quirks preserved (no length normalisation, finished beams keep extending --
         the reference's `is True` test never fires --, last seqs slot never written, stable tie order).
@@ -551,18 +577,25 @@ class GPV(nn.Module):
         reported probability) and vocab_mask ([V] fp32 added to every row of logits).
         phrases (a phrases.PhraseSet): the answer is one of the set's phrases -- the device path with gpv_phrase_step (hip_phrase; the
         rule: gpv1_amd.phrases) in place of gpv_beam_step; '_beam_phrase' [B,K] int32 (the phrase a slot spelled, -1 for a slot
-        that holds none) is added, 'answer_probs' are the model's probabilities of phrase + __stop__ over the whole vocabulary."""
+        that holds none) is added, 'answer_probs' are the model's probabilities of phrase + __stop__ over the whole vocabulary.
+        no_repeat_ngram (n: no hypothesis writes an n-gram twice), min_length (__stop__ is banned before that many tokens) and
+        repetition_penalty (theta: the logit of a token the hypothesis already holds is multiplied by theta when negative, by 1 / theta
+        otherwise; None or 1.0: off) act inside gpv_beam_step on every hypothesis's own history (the rule: gpv1_amd.beam, THE
+        CONSTRAINTS); an argument that is None falls back to cfg['beam'], then to off.  They need impl='device' and exclude phrases."""
         if phrases is not None:
+            self._beam_constraints(beam_size, impl, vocab_mask, phrases, no_repeat_ngram, min_length, repetition_penalty)
             return self._forward_phrases(images, queries, beam_size, phrases, vocab_mask, impl, finished, length_penalty)
         impl, finished, alpha = self._beam_options(impl, finished, length_penalty, vocab_mask)
-        kw = dict(impl=impl, finished=finished, alpha=alpha)
+        constr = self._beam_constraints(beam_size, impl, vocab_mask, None, no_repeat_ngram, min_length, repetition_penalty)
+        kw = dict(impl=impl, finished=finished, alpha=alpha, **({'constraints': constr} if constr else {}))
         outputs = None
         if (not self.training and not torch.is_grad_enabled() and self.cfg.get('graph_inference', True)
                 and self.cfg.get('kv_decode', True)):
             # the whole beam search (encoder + 19 KV-cached steps with their top-k / sort / cache reordering) has static
             # shapes: one hipGraph, like the greedy path
             queries = self._host_tokenize(images, queries)
-            outputs = self._graphed(('beam', beam_size, impl, finished, alpha),
+            # (the constraints are part of the key: a captured search is never replayed with other settings)
+            outputs = self._graphed(('beam', beam_size, impl, finished, alpha) + ((tuple(sorted(constr.items())),) if constr else ()),
                                     lambda im, q, vm, qe: self._beam_device(im, q, beam_size, vocab_mask=vm, **kw), images, queries, vocab_mask)
         if outputs is None:
             outputs = self._beam_device(images, queries, beam_size, vocab_mask=vocab_mask, **kw)
@@ -696,7 +729,7 @@ class GPV(nn.Module):
             if t + 1 < T - 1:                                                  # (nothing reads the caches after the last step)
                 kv.reorder_device(parent, t + 1)
 
-    def _beam_device(self, images, queries, beam_size, vocab_mask=None, impl='torch', finished='extend', alpha=0.0):
+    def _beam_device(self, images, queries, beam_size, vocab_mask=None, impl='torch', finished='extend', alpha=0.0, constraints=None):
         """device part of the beam search: outputs dict + '_beam_seqs' [K,B,T] + '_beam_lp' [B,K] (no host round trip)"""
         outputs, memory = self._encode(images, queries, self._bert_fork(images, queries) if self._capturing(images, queries) else None)
         B, K, T = memory.shape[0], beam_size, self.cfg.max_text_len
@@ -715,7 +748,9 @@ class GPV(nn.Module):
             if kv is None:
                 raise RuntimeError("forward_beam_search: impl='device' needs the KV-cached decoder (eval mode, no grad, cfg kv_decode); "
                                    "there is no fallback to the torch path")
-            return self._beam_steps_device(outputs, kv, B, K, T, vocab_mask, finished, alpha)
+            return self._beam_steps_device(outputs, kv, B, K, T, vocab_mask, finished, alpha, constraints or {})
+        if constraints:
+            raise ValueError("forward_beam_search: the constraints need impl='device'")
         for t in range(T - 1):
             if kv is not None:
                 kv.tok.copy_(tok[:, :, -1].reshape(K * B))
@@ -742,8 +777,8 @@ class GPV(nn.Module):
         outputs['_beam_seqs'], outputs['_beam_lp'] = seqs, seq_lp
         return outputs
 
-    def _beam_steps_device(self, outputs, kv, B, K, T, vocab_mask, finished, alpha):
-        """the device path of the plain search: _device_steps with gpv_beam_step"""
+    def _beam_steps_device(self, outputs, kv, B, K, T, vocab_mask, finished, alpha, constraints):
+        """the device path of the plain search: _device_steps with gpv_beam_step (constraints: the keywords of _beam_constraints, {} = off)"""
         from . import beam as rule, hip_beam
         rule.check_extents(K, len(self.vocab), T)
         dev = kv.tok.device
@@ -757,7 +792,7 @@ class GPV(nn.Module):
         parent, fin, length = i32(B, K), i32(B, K), i32(B, K)
         mode, pad, stop = rule.MODES[finished], self.word_to_idx['__pad__'], self.word_to_idx['__stop__']
         self._device_steps(kv, T, parent, lambda t, logits: hip_beam.step(logits, lse, seq_lp, seqs, kv.tok, parent, fin, length, t, mode,
-                                                                          pad, stop, inv_pen=inv_pen, vocab_mask=vocab_mask))
+                                                                          pad, stop, inv_pen=inv_pen, vocab_mask=vocab_mask, **constraints))
         outputs['_beam_seqs'], outputs['_beam_lp'] = seqs, seq_lp
         outputs['beam_lengths'], outputs['beam_finished'] = length, fin
         return outputs

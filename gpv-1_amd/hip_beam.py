@@ -24,7 +24,8 @@ class BeamArgs(C.Structure):
     _fields_ = [('logits', C.c_void_p), ('pitch', C.c_int64), ('vocab_mask', C.c_void_p), ('inv_pen', C.c_void_p), ('lse', C.c_void_p),
                 ('seq_lp', C.c_void_p), ('seqs', C.c_void_p), ('tok', C.c_void_p), ('parent', C.c_void_p), ('finished', C.c_void_p),
                 ('length', C.c_void_p), ('B', C.c_int), ('K', C.c_int), ('V', C.c_int), ('T', C.c_int), ('t', C.c_int),
-                ('mode', C.c_int), ('pad_id', C.c_int), ('stop_id', C.c_int), ('dtype', C.c_int)]
+                ('mode', C.c_int), ('pad_id', C.c_int), ('stop_id', C.c_int), ('dtype', C.c_int), ('no_repeat', C.c_int),
+                ('min_len', C.c_int), ('rep_neg', C.c_float), ('rep_pos', C.c_float)]
 
 
 class ReorderArgs(C.Structure):
@@ -68,18 +69,25 @@ def step_fields(module, logits, lse, seq_lp, seqs, tok, parent, length, inv_pen,
                 B=B, K=K, V=V, T=T, dtype=_DTYPES[logits.dtype]), K, B, T, V
 
 
-def step(logits, lse, seq_lp, seqs, tok, parent, finished, length, t, mode, pad_id, stop_id, inv_pen=None, vocab_mask=None):
+def step(logits, lse, seq_lp, seqs, tok, parent, finished, length, t, mode, pad_id, stop_id, inv_pen=None, vocab_mask=None,
+         no_repeat_ngram=0, min_length=0, repetition=None):
     """gpv_beam_step on the current stream: one launch, no sync, everything in place.  logits [K*B, V] bf16 / fp32 with unit column
     stride (any row pitch >= V: a view of the decoder's [K*B, T, V] buffer), lse [K*B] fp32 out, seq_lp [B,K] fp32, seqs [K,B,T] int64,
-    tok [K*B] int64 out, parent [B,K] int32 out, finished / length [B,K] int32; inv_pen [T+1] fp32 or None, vocab_mask [V] fp32 or None."""
-    f, K, B, T, V = step_fields('hip_beam', logits, lse, seq_lp, seqs, tok, parent, length, inv_pen,
-                                lambda K, V, T: rule.check_extents(K, V, T, t))
+    tok [K*B] int64 out, parent [B,K] int32 out, finished / length [B,K] int32; inv_pen [T+1] fp32 or None, vocab_mask [V] fp32 or None.
+    The constraints of the rule: no_repeat_ngram (n, 0 = off), min_length (0 = off), repetition (the (rep_neg, rep_pos) pair of
+    beam.rep_factors, None = off)."""
+    def extents(K, V, T):
+        rule.check_extents(K, V, T, t)
+        rule.check_constraints(V, T, no_repeat_ngram, min_length, repetition)
+    f, K, B, T, V = step_fields('hip_beam', logits, lse, seq_lp, seqs, tok, parent, length, inv_pen, extents)
+    rep_neg, rep_pos = (0.0, 0.0) if repetition is None else repetition
     if mode not in (rule.EXTEND, rule.FREEZE):
         raise ValueError(f'hip_beam.step: mode must be EXTEND (0) or FREEZE (1), got {mode!r}')
     if not (0 <= pad_id < V and 0 <= stop_id < V):
         raise ValueError(f'hip_beam.step: pad_id / stop_id must lie in the vocabulary, got {pad_id} / {stop_id} of {V}')
     a = BeamArgs(vocab_mask=None if vocab_mask is None else _want('vocab_mask', vocab_mask, torch.float32, (V,)),
-                 finished=_want('finished', finished, torch.int32, (B, K)), t=t, mode=mode, pad_id=pad_id, stop_id=stop_id, **f)
+                 finished=_want('finished', finished, torch.int32, (B, K)), t=t, mode=mode, pad_id=pad_id, stop_id=stop_id,
+                 no_repeat=int(no_repeat_ngram), min_len=int(min_length), rep_neg=float(rep_neg), rep_pos=float(rep_pos), **f)
     _chk(lib().gpv_beam_step(C.byref(a), _stream()), 'gpv_beam_step')
 
 

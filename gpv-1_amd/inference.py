@@ -117,10 +117,12 @@ def decode_outputs(outputs, model, num_output_boxes=None):
 
 
 def beam_options(beam):
-    """the `beam` group of a config (added keys beam.impl / beam.finished / beam.length_penalty) as forward_beam_search's keywords;
-    a key that is absent is left to the model's own defaults (its cfg['beam'], GPV_BEAM)"""
+    """the `beam` group of a config (added keys beam.impl / beam.finished / beam.length_penalty / beam.no_repeat_ngram /
+    beam.min_length / beam.repetition_penalty) as forward_beam_search's keywords; a key that is absent is left to the model's own
+    defaults (its cfg['beam'], GPV_BEAM)"""
     beam = beam or {}
-    names = {'impl': 'impl', 'finished': 'finished', 'length_penalty': 'length_penalty'}
+    names = {'impl': 'impl', 'finished': 'finished', 'length_penalty': 'length_penalty', 'no_repeat_ngram': 'no_repeat_ngram',
+             'min_length': 'min_length', 'repetition_penalty': 'repetition_penalty'}
     return {kw: beam.get(k) for k, kw in names.items() if beam.get(k, None) is not None}
 
 
@@ -172,7 +174,8 @@ def main(argv=None):
     ap.add_argument('--config', default=None, help='YAML file (e.g. the reference configs/exp/gpv.yaml); default: gpv1_amd.default_config')
     ap.add_argument('overrides', nargs='*')
     args = ap.parse_args(argv)
-    # outputs.vis= ckpt= inputs.img= inputs.query= inputs.answers= beam_size= beam.impl= beam.finished= beam.length_penalty= are added keys
+    # outputs.vis= ckpt= inputs.img= inputs.query= inputs.answers= beam_size= beam.impl= beam.finished= beam.length_penalty=
+    # beam.no_repeat_ngram= beam.min_length= beam.repetition_penalty= are added keys
     cfg = load_config(args.config, args.overrides, strict=False) if args.config else from_dict(default_tree(), args.overrides, strict=False)
     model = GPV(cfg.model).cuda().eval()
     load_model_state(model, cfg.get('ckpt', cfg.eval.ckpt), map_location='cuda:0')

@@ -58,6 +58,22 @@ def _answer_loop(model, batches, samples, limit, vocab_mask=None):
     return answers[:n]
 
 
+def _beam_answers(model, batches, samples, limit, beam_size, beam=None):
+    """-> slot 0 of GPV.forward_beam_search (the best hypothesis, its words up to __stop__ / __pad__) of the first min(limit,
+    len(samples)) samples, detokenised"""
+    from .inference import beam_options
+    dev = _device(model)
+    n = len(samples) if limit is None else min(int(limit), len(samples))
+    model.eval()
+    answers = []
+    for imgs, queries, _ in batches:
+        if len(answers) >= n:
+            break
+        outputs = model.forward_beam_search(_images(imgs, dev), queries, beam_size=beam_size, **beam_options(beam))
+        answers.extend(detokenize(hyps[0]) for hyps in outputs['answers'])
+    return answers[:n]
+
+
 @torch.no_grad()
 def vqa_accuracy(model, batches, samples, limit=None):
     """metrics.py:15-66 -> soft VQA accuracy, rounded to 4 places"""
@@ -66,10 +82,15 @@ def vqa_accuracy(model, batches, samples, limit=None):
 
 
 @torch.no_grad()
-def cap_metrics(model, batches, samples, limit=None, scorer=None):
+def cap_metrics(model, batches, samples, limit=None, scorer=None, beam_size=None, beam=None):
     """metrics.py:68-119 -> (scores, predictions): predictions = {str(cap_id): {'answer': str}}; scores = scorer(samples, predictions)
-    (the reference's {'Bleu1'.., 'Cider'}) or {} without a scorer"""
-    answers = _answer_loop(model, batches, samples, limit)
+    (the reference's {'Bleu1'.., 'Cider'}) or {} without a scorer.  beam_size / beam (added; the keys of inference.beam_options, among
+    them no_repeat_ngram, min_length, repetition_penalty): the caption is the best hypothesis of GPV.forward_beam_search, cut at the
+    first __stop__ / __pad__; the default stays the greedy decode, unchanged"""
+    if beam_size:
+        answers = _beam_answers(model, batches, samples, limit, int(beam_size), beam)
+    else:
+        answers = _answer_loop(model, batches, samples, limit)
     predictions = {str(s['cap_id']): {'answer': a} for s, a in zip(samples, answers)}
     return (scorer(samples, predictions) if scorer is not None else {}), predictions
 

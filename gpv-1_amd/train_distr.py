@@ -142,8 +142,10 @@ def _eval_cls(model, batches_, ds, limit):
     return metrics.cls_metrics(model, batches_, ds.samples, limit, synonyms=getattr(ds, 'synonyms', None))
 
 
-def _eval_cap(model, batches_, ds, limit, mode=None):
-    """mode: cfg.training.caption_scorer -- 'device' | 'host' builds a caption_scorer.CaptionScorer when the dataset carries no scorer"""
+def _eval_cap(model, batches_, ds, limit, mode=None, caption_beam=None):
+    """mode: cfg.training.caption_scorer -- 'device' | 'host' builds a caption_scorer.CaptionScorer when the dataset carries no scorer.
+    caption_beam: cfg.training.caption_beam -- absent: greedy captions, as the reference; a group of `size` and the beam.* keys of
+    inference.beam_options: captions by beam search (metrics.cap_metrics)"""
     from . import metrics
     scorer = getattr(ds, 'scorer', None)
     if scorer is None and mode is not None:
@@ -151,7 +153,12 @@ def _eval_cap(model, batches_, ds, limit, mode=None):
             raise ValueError(f"training.caption_scorer must be 'device' or 'host', got {mode!r}")
         from .caption_scorer import CaptionScorer
         scorer = CaptionScorer(device=None if mode == 'host' else metrics._device(model), host=mode == 'host')
-    scores, _ = metrics.cap_metrics(model, batches_, ds.samples, limit, scorer=scorer)
+    if caption_beam:
+        beam = {k: v for k, v in dict(caption_beam).items() if k != 'size'}
+        scores, _ = metrics.cap_metrics(model, batches_, ds.samples, limit, scorer=scorer, beam_size=int(dict(caption_beam).get('size') or 1),
+                                        beam=beam)
+    else:
+        scores, _ = metrics.cap_metrics(model, batches_, ds.samples, limit, scorer=scorer)
     return scores
 
 
@@ -188,7 +195,8 @@ def evaluate_subset(model, datasets, subset, cfg, epoch, device, log=print, said
                     log(f'Eval not implemented for {name}')
                     continue
                 if fn is _eval_cap:
-                    out = fn(model, eval_batches(ds, batch_size, device), ds, limits.get(name, None), tr_cfg.get('caption_scorer', None))
+                    out = fn(model, eval_batches(ds, batch_size, device), ds, limits.get(name, None), tr_cfg.get('caption_scorer', None),
+                             tr_cfg.get('caption_beam', None))
                 else:
                     out = fn(model, eval_batches(ds, batch_size, device), ds, limits.get(name, None))
                 if name == 'coco_vqa':

@@ -26,6 +26,27 @@
  * Caller conditions: 1 <= K <= GPV_BEAM_MAX_K, K <= V, T <= GPV_BEAM_MAX_T; a mask leaves at least K finite entries per row; a
  * NaN logit gives an undefined selection (every index written stays inside its array; no loop bound depends on the data).
  *
+ * THE CONSTRAINTS (no_repeat, min_len, rep_neg / rep_pos; all zero: off, and the rule is the one above).  They add to steps 1-3;
+ * steps 4-7 are unchanged.  h = seqs[k1, b, 0:t] is the history of the row's parent: the tokens written so far (__cls__ is not part
+ * of it; special tokens in it count like any other token).  A frozen parent (mode FREEZE with finished[b,k1] set) is exempt from
+ * everything below; it still has its single pad_id candidate.
+ *  1b. Repetition penalty, on when rep_neg and rep_pos are non-zero, after the mask add: for every v that occurs in h,
+ *      x_v = x_v < 0 ? x_v * rep_neg : x_v * rep_pos: one fp32 multiply, applied once however often v occurs.  rep_neg = fp32(theta),
+ *      rep_pos = fp32(1 / theta), computed in float64 on the host (gpv1_amd.beam.rep_factors): a multiply, not a divide, so that host
+ *      and device round the same way.  -inf stays -inf.
+ *  2.  m and lse_r are taken over ALL v of the row as it stands after 1b, banned tokens included: bans do not renormalise.  The first
+ *      pop is no longer the row maximum when the maximum is banned, so m has a reduction of its own.  The summation order is the
+ *      one pinned below, unchanged.
+ *  3a. The banned set of the row.  (i) n = no_repeat >= 1 and t >= n - 1: with p = h[t-n+1 : t] (n - 1 tokens, empty for n = 1),
+ *      for every i in 0 .. t-n with h[i : i+n-1] == p the token h[i+n-1] is banned (at most t - n + 1 bans; t = 0 bans nothing).
+ *      (ii) stop_id is banned while length[b,k1] < min_len: at least min_len tokens precede __stop__.
+ *  3.  The row's candidates are its K largest x_v AMONG THE TOKENS THAT ARE NOT BANNED, ties to the lower v; lp = x_v - lse_r.
+ * Caller condition with a constraint on: every row keeps at least K entries that are finite and not banned (a row bans fewer than T
+ * tokens, so a mask that leaves K + T finite entries, or V >= K + T without one, suffices).  Below it the selection is undefined
+ * (every index written stays inside its array; no loop bound depends on the data).  Extents: 0 <= no_repeat <= GPV_BEAM_MAX_NGRAM,
+ * 0 <= min_len <= T, rep_neg and rep_pos both zero or both finite and positive, and with any constraint on V <= GPV_BEAM_MAX_CONSTR_V
+ * (a "seen" and a "banned" bitmap of V bits each in LDS, 16 KB together).
+ *
  * THE SUM OF STEP 2.  256 lanes; lane l adds expf(x_v - m) for v = l, l + 256, l + 512, ... in ascending v onto 0.f, the 64 lanes
  * of a wave are folded by xor butterflies (32, 16, 8, 4, 2, 1), the four wave sums are added one after the other in wave order.
  * The longest chain of dependent fp32 additions is therefore  n_chain(V) = ceil(V / 256) + 6 + 3. */
@@ -40,6 +61,8 @@ extern "C" {
 #define GPV_BEAM_MAX_T 64       /* max_text_len */
 #define GPV_BEAM_MAX_LAYERS 8   /* decoder layers of one gpv_beam_reorder call */
 #define GPV_BEAM_LANES 256      /* threads of a gpv_beam_step workgroup: the stride of the sum of step 2 */
+#define GPV_BEAM_MAX_NGRAM 8    /* largest no_repeat */
+#define GPV_BEAM_MAX_CONSTR_V 65536   /* largest V with a constraint on */
 
 #define GPV_BEAM_EXTEND 0       /* finished hypotheses keep extending (the reference) */
 #define GPV_BEAM_FREEZE 1       /* a hypothesis that emitted stop_id keeps its score and is followed by pad_id */
@@ -63,13 +86,19 @@ typedef struct gpv_beam_args {
   int mode;                     /* GPV_BEAM_EXTEND / GPV_BEAM_FREEZE */
   int pad_id, stop_id;          /* in [0, V) */
   int dtype;                    /* of logits: GPV_BEAM_BF16 / GPV_BEAM_F32 */
+  int no_repeat;                /* n of step 3a (i): no n-gram is written twice; 0 = off */
+  int min_len;                  /* step 3a (ii): stop_id is banned while length < min_len; 0 = off */
+  float rep_neg, rep_pos;       /* step 1b: fp32(theta), fp32(1 / theta); both 0 = off */
 } gpv_beam_args;
 
 /* One launch, one workgroup of GPV_BEAM_LANES threads per batch element.  Per row every thread keeps a sorted top-K list over
  * its strided elements, the workgroup pops K winners with (value, index) arg-max reductions (the first is the row maximum) and
  * sums the exponentials; the K*K candidates (one wave) are ranked by counting how many candidates beat each one; the workgroup
  * stages the K seqs rows of its b in LDS before it writes them back, so seqs, seq_lp, finished and length are updated in place.
- * Every load is from a clamped index and padded at use.  B = 0: nothing is launched. */
+ * Every load is from a clamped index and padded at use.  B = 0: nothing is launched.
+ * With a constraint on, another instantiation runs: per row the workgroup marks the history's tokens in the seen bitmap and the row's
+ * bans in the banned bitmap (LDS; the words it touched are zeroed again behind the row), applies 1b at every load of both passes, keeps
+ * banned tokens out of the lane lists and reduces m over the whole row.  Still one launch. */
 int gpv_beam_step(const gpv_beam_args* a, void* stream);
 
 typedef struct gpv_beam_reorder_args {

@@ -2,6 +2,7 @@
 (GPV.forward_beam_search impl='torch' / 'device', gpv-1_amd/csrc/beam_step.hip), the whole search one hipGraph.
 
   python tools/bench_beam.py [--out profiles/r13_beam.txt] [--passes 5] [--reps 3] [--no-trace]
+                             [--no-repeat N] [--min-length M] [--repetition-penalty THETA]
 
 The two paths alternate in one process, `--passes` passes of `--reps` searches each (per-search wall time incl. the host detokenisation,
 as bench.py times it); median and min - max of the passes are reported.  Then ONE `rocprofv3 --kernel-trace` run of a fresh child process
@@ -10,7 +11,11 @@ durations of the two new kernels.  How the launches are counted: a device-path s
 records between two consecutive step_kernels are one step (decoder core + 2); the child runs device, device, torch, device searches, and
 the records between the last step_kernel of one device search and the first of the next are (tail + head) without and with a torch
 search in between -- the difference is the torch search, from which the head (encoder, cross-attention K | V, the first step's core) and
-T - 1 decoder cores are taken off."""
+T - 1 decoder cores are taken off.
+
+A last section times gpv_beam_step alone with device events at the search's shapes (B = 64, K = 5, the model's vocabulary, bf16 logits
+of pitch T*V, the longest history t = T - 2).  --no-repeat / --min-length / --repetition-penalty (the constraints of gpv1_amd.beam) add
+a third path to the alternation, the device path with these options, and to that section each given option alone and all together."""
 import argparse
 import csv
 import glob
@@ -95,8 +100,36 @@ def analyse(trace_dir, T):
     return out
 
 
+def step_times(torch, V, T, variants, runs=7, launches=200):
+    """gpv_beam_step alone, device events around `launches` launches, `runs` times -> {name: [us per launch]}; the variants alternate"""
+    import gpv1_amd.hip_beam as hip_beam
+    dev = torch.device('cuda:0')
+    g = torch.Generator(device='cpu').manual_seed(0)
+    t = T - 2
+    buf = (3.0 * torch.randn(K * BATCH, T, V, generator=g)).to(torch.bfloat16).to(dev)
+    alphabet = torch.randint(0, V - 4, (3,), generator=g)
+    seqs0 = alphabet[torch.randint(0, 3, (K, BATCH, T), generator=g)].to(dev)
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    out = {name: [] for name in variants}
+    for _ in range(runs + 1):                                                # (the first round is the warm-up)
+        for name, kw in variants.items():
+            seq_lp, seqs, lse = torch.zeros(BATCH, K, device=dev), seqs0.clone(), torch.zeros(K * BATCH, device=dev)
+            tok, parent, fin, length = torch.zeros(K * BATCH, dtype=torch.long, device=dev), i32(BATCH, K), i32(BATCH, K), i32(BATCH, K) + t
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(launches):
+                hip_beam.step(buf[:, t], lse, seq_lp, seqs, tok, parent, fin, length, t, 0, V - 4, V - 2, **kw)
+            e1.record()
+            torch.cuda.synchronize()
+            out[name].append(e0.elapsed_time(e1) / launches * 1e3)
+    return {name: ts[1:] for name, ts in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--no-repeat', type=int, default=0, help='no_repeat_ngram of the constrained path')
+    ap.add_argument('--min-length', type=int, default=0, help='min_length of the constrained path')
+    ap.add_argument('--repetition-penalty', type=float, default=None, help='repetition_penalty of the constrained path')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r13_beam.txt'))
     ap.add_argument('--passes', type=int, default=5)
     ap.add_argument('--reps', type=int, default=3)
@@ -108,11 +141,16 @@ def main():
     torch, model, samples, q = setup()
     T = model.cfg.max_text_len
     times = {'torch': [], 'device': []}
+    constr = {k: v for k, v in (('no_repeat_ngram', args.no_repeat), ('min_length', args.min_length),
+                                ('repetition_penalty', args.repetition_penalty)) if v}
+    paths = {'torch': dict(impl='torch'), 'device': dict(impl='device')}
+    if constr:
+        times['constrained'], paths['constrained'] = [], dict(impl='device', **constr)
     with torch.no_grad():
         outs = {}
-        for impl in times:                                                   # warm-up + capture of both graphs
+        for impl in times:                                                   # warm-up + capture of the graphs
             for _ in range(2):
-                outs[impl] = model.forward_beam_search(samples, q, beam_size=K, impl=impl)
+                outs[impl] = model.forward_beam_search(samples, q, beam_size=K, **paths[impl])
         torch.cuda.synchronize()
         same = sum(a == b for x, y in zip(outs['torch']['answers'], outs['device']['answers']) for a, b in zip(x, y))
         for _ in range(args.passes):
@@ -120,18 +158,33 @@ def main():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(args.reps):
-                    model.forward_beam_search(samples, q, beam_size=K, impl=impl)
+                    model.forward_beam_search(samples, q, beam_size=K, **paths[impl])
                 torch.cuda.synchronize()
                 times[impl].append((time.perf_counter() - t0) / args.reps * 1e3)
     lines = [f'# tools/bench_beam.py: forward_beam_search(beam_size={K}) of {BATCH} synthetic 480x640 images, bf16, V = {len(model.vocab)}, T = {T}, the whole search one hipGraph',
              f'# {args.passes} alternating passes of {args.reps} searches per path, per-search wall time incl. host detokenisation']
     for impl, ts in times.items():
-        lines.append(f'{impl:7s} median {statistics.median(ts):.3f} ms   min {min(ts):.3f}   max {max(ts):.3f}   passes ' + ' '.join(f'{t:.3f}' for t in ts))
+        lines.append(f'{impl:11s} median {statistics.median(ts):.3f} ms   min {min(ts):.3f}   max {max(ts):.3f}   passes ' + ' '.join(f'{t:.3f}' for t in ts))
+    variants = {'plain': {}}
+    if constr:
+        from gpv1_amd import beam as rule
+        lines.insert(2, '# constrained = the device path with ' + ' '.join(f'{k}={v}' for k, v in constr.items()))
+        single = {'no_repeat_ngram': dict(no_repeat_ngram=args.no_repeat), 'min_length': dict(min_length=args.min_length),
+                  'repetition_penalty': dict(repetition=rule.rep_factors(args.repetition_penalty))}
+        given = {k: single[k] for k in constr}
+        variants.update({f'{k} alone': kw for k, kw in given.items()})
+        if len(given) > 1:
+            variants['all together'] = {k: v for kw in given.values() for k, v in kw.items()}
+    V = len(model.vocab)
+    step_lines = [f'gpv_beam_step alone (B = {BATCH}, K = {K}, V = {V}, bf16, pitch T*V, t = T - 2 = {T - 2}; device events, 7 runs of 200 launches, us per launch):']
+    for name, ts in step_times(torch, V, T, variants).items():
+        step_lines.append(f'  {name:24s} median {statistics.median(ts):.2f}   min {min(ts):.2f}   max {max(ts):.2f}')
     spread = max(max(ts) - min(ts) for ts in times.values())
     d = statistics.median(times['device']) - statistics.median(times['torch'])
     lines.append(f'device - torch = {d:+.3f} ms (largest min - max spread of a path in this run: {spread:.3f} ms): '
                  + ('device path not slower than the spread' if d <= spread else 'DEVICE PATH SLOWER than the spread'))
     lines.append(f'hypotheses with identical words on both paths: {same} of {BATCH * K} (bf16 logits of random weights tie inside the top-(K+1) of a row in 40 % of the rows: the rule takes the lower index, torch.topk either; 320 of 320 in precise mode)')
+    lines += step_lines
     del model, samples, q
     torch.cuda.empty_cache()
     if not args.no_trace:
