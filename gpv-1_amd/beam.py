@@ -41,14 +41,40 @@ tokens, so a mask that leaves K + T finite entries, or V >= K + T without one, s
 (every index written stays inside its array; no loop bound depends on the data).  Extents: 0 <= no_repeat <= GPV_BEAM_MAX_NGRAM,
 0 <= min_len <= T, rep_neg and rep_pos both zero or both finite and positive, and with any constraint on V <= GPV_BEAM_MAX_CONSTR_V
 (a "seen" and a "banned" bitmap of V bits each in LDS, 16 KB together).
+
+THE SAMPLER (mode GPV_BEAM_SAMPLE: N draws per batch element in place of a beam).  Step t, batch element b, slot k = 0..K-1: the slots
+are the N samples of b, so N = K <= GPV_BEAM_MAX_K; logits row r = k*B + b.  lse, cand_v and cand_w are written for every row, finished
+or not.
+ 1. Temperature and mask.  x_v = fp32(logit[r, v]) * inv_temp: one fp32 multiply; inv_temp = fp32(1 / temperature), computed in
+    float64 on the host; field value 0 means temperature 1: no multiply.  Then + vocab_mask[v]: one fp32 add; no add when the mask
+    is absent.
+ 2. Normalisation.  m and lse_r are taken over all v of the row as it stands after step 1, in the summation order pinned below.  lse
+    is an OUTPUT of the device and an INPUT of the host rule.
+ 3. Candidates: the C = top_k largest x_v, ties to the lower v, rank j = 0..C-1; 1 <= C <= GPV_BEAM_MAX_C, C <= V.
+    lp_j = x_j - lse_r: one fp32 subtract.  w_j = expf(lp_j) is evaluated on the device only.  cand_v[r, j] (int32) and cand_w[r, j]
+    (fp32), both [K*B, C], are OUTPUTS of the step; cand_w is an INPUT of the host rule, which recomputes cand_v and lp itself.
+ 4. Nucleus.  c_j = c_{j-1} + w_j, c_{-1} = 0: serial fp32 additions in rank order.  n = 1 + #{ j in 0..C-2 : c_j < top_p }.  Field
+    value 0 means off: n = C.  Otherwise 0 < top_p < 1.
+ 5. Draw.  bits = hash_u32(seed, ((uint64) t * B + b) * K + k), the function of csrc/common.h.  seed is read from a DEVICE pointer
+    that holds one value: the caller rewrites it between replays, so a captured search draws anew each time.
+    u = fp32(bits >> 8) * 2^-24, which is exact.  tau = u * c_{n-1}: one fp32 multiply.  j* = the first j < n with c_j > tau; if there
+    is none, j* = n - 1.
+ 6. Finished slots behave as FREEZE does: with finished[b,k] set the token is pad_id, seq_lp and length stay unchanged.
+ 7. Write.  parent[b,k] = k.  seq_lp'[b,k] = seq_lp[b,k] + lp_{j*}: one fp32 add.  seqs'[k,b,t] = tok[k*B+b] = cand_v[r, j*].
+    length' = length + 1.  finished' = finished | (token == stop_id).  No -1e9 rule at t = 0: the K slots differ by their draw.
+Caller conditions: a mask leaves at least C finite entries per row; inv_pen, no_repeat, min_len and rep_* must be off in this mode
+and are refused otherwise.  The reported seq_lp is the model's log-probability of the sequence at that temperature, over the whole
+vocabulary -- what the beam search reports -- not the probability under the truncated sampler.  The sampler is truncated to at most
+GPV_BEAM_MAX_C candidates; pure sampling over all of V does not exist.
 """
 import math
 
 import numpy as np
 
-EXTEND, FREEZE = 0, 1
+EXTEND, FREEZE, SAMPLE = 0, 1, 2          # GPV_BEAM_EXTEND, GPV_BEAM_FREEZE, GPV_BEAM_SAMPLE
 MODES = {'extend': EXTEND, 'freeze': FREEZE}
 MAX_K, MAX_T = 8, 64          # GPV_BEAM_MAX_K, GPV_BEAM_MAX_T
+MAX_C = 64                    # GPV_BEAM_MAX_C
 MAX_NGRAM, MAX_CONSTR_V = 8, 65536      # GPV_BEAM_MAX_NGRAM, GPV_BEAM_MAX_CONSTR_V
 LANES = 256                   # GPV_BEAM_LANES
 F32 = np.float32
@@ -249,3 +275,127 @@ def beam_search_host(step_logits_fn, B, K, T, cls_id, pad_id, stop_id, mode=EXTE
         seqs, seq_lp, finished, length = o['seqs'], o['seq_lp'], o['finished'], o['length']
     keys = seq_lp if inv_pen is None else (seq_lp * inv_pen[np.clip(length, 0, T)]).astype(F32)
     return {'seqs': seqs, 'seq_lp': seq_lp, 'finished': finished, 'length': length, 'keys': keys}
+
+
+# ---- THE SAMPLER -------------------------------------------------------------------------------------------------------------------
+def hash_u32(seed, idx):
+    """csrc/common.h hash_u32 on numpy integers (lowbias32 finalizer on index ^ seed, high words folded in) -> uint64 array < 2^32"""
+    M = np.uint64(0xFFFFFFFF)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    idx = np.asarray(idx).astype(np.uint64)
+    x = (idx & M) ^ np.uint64(seed & 0xFFFFFFFF)
+    x = x ^ ((((idx >> np.uint64(32)) & M) ^ np.uint64(seed >> 32)) * np.uint64(0x9E3779B9) & M)
+    x = x ^ (x >> np.uint64(16)); x = (x * np.uint64(0x7FEB352D)) & M
+    x = x ^ (x >> np.uint64(15)); x = (x * np.uint64(0x846CA68B)) & M
+    return x ^ (x >> np.uint64(16))
+
+
+def draw_u(seed, t, b, k, B, K):
+    """step 5: u = fp32(bits >> 8) * 2^-24 of slot (t, b, k), exact"""
+    bits = int(hash_u32(seed, (int(t) * int(B) + int(b)) * int(K) + int(k)))
+    return F32(bits >> 8) * F32(2.0 ** -24)
+
+
+def inv_temperature(temperature):
+    """inv_temp = fp32(1 / temperature) of step 1, computed in float64; None for temperature None or 1.0 (no multiply)"""
+    if temperature is None or float(temperature) == 1.0:
+        return None
+    temperature = float(temperature)
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError(f'sampler: the temperature must be finite and positive, got {temperature!r} (use top_k=1 for the arg-max)')
+    return F32(1.0 / temperature)
+
+
+def check_sampler(K, V, T, t, top_k, top_p=None, inv_temp=None, inv_pen=None, no_repeat_ngram=0, min_length=0, repetition=None):
+    """the extents of one sampled step; the beam's own rules (a length penalty table, the constraints) are refused in this mode"""
+    check_extents(K, V, T, t)
+    C = int(top_k)
+    if not 1 <= C <= MAX_C:
+        raise ValueError(f'sampler: 1 <= top_k <= {MAX_C} is supported (GPV_BEAM_MAX_C; sampling over the whole vocabulary does not exist), got {top_k}')
+    if C > V:
+        raise ValueError(f'sampler: top_k {C} exceeds the vocabulary ({V})')
+    if top_p is not None and not 0.0 < float(F32(top_p)) < 1.0:
+        raise ValueError(f'sampler: top_p must lie strictly between 0 and 1 (None: off), got {top_p!r}')
+    if inv_temp is not None and not (math.isfinite(float(inv_temp)) and float(F32(inv_temp)) > 0.0 and math.isfinite(float(F32(inv_temp)))):
+        raise ValueError(f'sampler: inv_temp must be finite and positive (inv_temperature; None: temperature 1), got {inv_temp!r}')
+    if inv_pen is not None:
+        raise ValueError('sampler: a length penalty does not combine with sampling (nothing is ranked; a follow-up)')
+    if int(no_repeat_ngram) != 0 or int(min_length) != 0 or repetition is not None:
+        raise ValueError('sampler: no_repeat_ngram / min_length / repetition do not combine with sampling (the sampled step is not taught '
+                         'the constraints; a follow-up)')
+
+
+def sample_step_host(logits, lse, cand_w, seq_lp, seqs, finished, length, t, pad_id, stop_id, seed, top_k, top_p=None, inv_temp=None,
+                     vocab_mask=None, u=None):
+    """One sampled step (THE SAMPLER above).  logits [K*B, V] (values exactly representable in fp32), lse [K*B] fp32 (the device's, or
+    any log-sum-exp of the rows as they stand after step 1), cand_w [K*B, C] fp32 (the device's expf(lp), or np.exp(lp) rounded to fp32),
+    seq_lp [B,K] fp32, seqs [K,B,T] int64, finished [B,K] 0/1, length [B,K] int; top_p / inv_temp None: off.  u ([B,K] fp32 or None):
+    the uniform numbers of step 5 in place of the hash (tests reach the fallback of step 5 with it).  Nothing is modified.
+    seq_lp is the model's log-probability of the sequence at that temperature over the whole vocabulary, as the beam search reports it;
+    it is NOT the probability under the truncated sampler.
+    -> dict(parent, tok, seqs, seq_lp, finished, length as beam_step_host; cand_v [K*B, C] int32, lp [K*B, C] fp32, n [B,K], pick [B,K])"""
+    x = np.asarray(logits, dtype=F32)
+    K, B, T = seqs.shape
+    V = x.shape[1]
+    C = int(top_k)
+    check_sampler(K, V, T, t, C, top_p, inv_temp)
+    if x.shape[0] != K * B:
+        raise ValueError(f'sampler: logits must have K*B = {K * B} rows, got {x.shape[0]}')
+    if inv_temp is not None:
+        x = x * F32(inv_temp)                                                    # step 1: one fp32 multiply
+    if vocab_mask is not None:
+        x = x + np.asarray(vocab_mask, dtype=F32)[None, :]                       # one fp32 add
+    lse = np.asarray(lse, dtype=F32)
+    w = np.asarray(cand_w, dtype=F32).reshape(K * B, C)
+    seq_lp = np.asarray(seq_lp, dtype=F32)
+    cand_v = np.argsort(-x, axis=1, kind='stable')[:, :C].astype(np.int32)       # step 3: C largest, ties to the lower v
+    lp = (np.take_along_axis(x, cand_v.astype(np.int64), axis=1) - lse[:, None]).astype(F32)      # one fp32 subtract
+    out = {'parent': np.tile(np.arange(K, dtype=np.int32), (B, 1)), 'tok': np.zeros(K * B, np.int64), 'seqs': np.array(seqs, dtype=np.int64),
+           'seq_lp': np.zeros((B, K), F32), 'finished': np.zeros((B, K), np.int32), 'length': np.zeros((B, K), np.int32),
+           'cand_v': cand_v, 'lp': lp, 'n': np.zeros((B, K), np.int32), 'pick': np.zeros((B, K), np.int32)}
+    p = None if top_p is None else F32(top_p)
+    for b in range(B):
+        for k in range(K):
+            r = k * B + b
+            c = np.zeros(C, F32)
+            acc = F32(0.0)
+            for j in range(C):                                                   # step 4: serial fp32 additions in rank order
+                acc = F32(acc + w[r, j])
+                c[j] = acc
+            n = C if p is None else 1 + int(np.sum(c[:C - 1] < p))
+            uu = draw_u(seed, t, b, k, B, K) if u is None else F32(np.asarray(u)[b, k])
+            tau = F32(uu * c[n - 1])                                             # step 5: one fp32 multiply
+            over = np.nonzero(c[:n] > tau)[0]
+            js = int(over[0]) if len(over) else n - 1
+            fin = bool(finished[b, k])
+            tokv = pad_id if fin else int(cand_v[r, js])                         # step 6
+            out['n'][b, k], out['pick'][b, k] = n, js
+            out['seq_lp'][b, k] = seq_lp[b, k] if fin else F32(seq_lp[b, k] + lp[r, js])        # step 7: one fp32 add
+            out['seqs'][k, b, t] = tokv
+            out['tok'][r] = tokv
+            out['length'][b, k] = int(length[b, k]) + (0 if fin else 1)
+            out['finished'][b, k] = int(fin or tokv == stop_id)
+    return out
+
+
+def sample_search_host(step_logits_fn, B, K, T, cls_id, pad_id, stop_id, seed, top_k, top_p=None, inv_temp=None, vocab_mask=None):
+    """The chained sampled search: step_logits_fn(t, tok [K,B,t+1] int64) -> logits [K*B, V] of the newest position (tok[:, :, 0] =
+    cls_id).  lse and cand_w are the host's (float64, rounded to fp32).  -> dict(seqs [K,B,T], seq_lp [B,K], finished, length)"""
+    seqs = np.zeros((K, B, T), np.int64)
+    seq_lp = np.zeros((B, K), F32)
+    finished = np.zeros((B, K), np.int32)
+    length = np.zeros((B, K), np.int32)
+    tok = np.full((K, B, 1), cls_id, np.int64)
+    for t in range(T - 1):
+        logits = np.asarray(step_logits_fn(t, tok), dtype=F32)
+        x = logits if inv_temp is None else logits * F32(inv_temp)
+        lse = lse_host(x, vocab_mask)
+        if vocab_mask is not None:
+            x = x + np.asarray(vocab_mask, dtype=F32)[None, :]
+        top = -np.sort(-x, axis=1, kind='stable')[:, :int(top_k)]
+        cand_w = np.exp((top - lse[:, None]).astype(F32).astype(np.float64)).astype(F32)
+        o = sample_step_host(logits, lse, cand_w, seq_lp, seqs, finished, length, t, pad_id, stop_id, seed, top_k, top_p=top_p,
+                             inv_temp=inv_temp, vocab_mask=vocab_mask)
+        tok = np.concatenate((tok, o['tok'].reshape(K, B, 1)), axis=-1)
+        seqs, seq_lp, finished, length = o['seqs'], o['seq_lp'], o['finished'], o['length']
+    return {'seqs': seqs, 'seq_lp': seq_lp, 'finished': finished, 'length': length}

@@ -226,4 +226,7 @@ inline bool check_step_common(const Args* a, int min_V) {
   return (int64_t)a->K * a->B <= 0x7fffffff / 2 && a->V <= (1 << 30);   // (32-bit element indices in the kernels)
 }
 
+// mode GPV_BEAM_SAMPLE of gpv_beam_step: its checks and its launch (sample_step.hip, libgpv_beam.so only)
+__attribute__((visibility("hidden"))) int launch_sample(const gpv_beam_args* a, void* stream);
+
 }  // namespace beam_core

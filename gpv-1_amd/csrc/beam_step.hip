@@ -15,6 +15,7 @@
 //                   keeps banned tokens out of the lane lists and reduces m over the whole row.  With every constraint off the plain
 //                   instantiations run, unchanged.
 //   reorder_kernel  one thread per (layer, b, position, 16-byte vector of the k | v columns): K loads, then K stores.
+// Mode GPV_BEAM_SAMPLE of gpv_beam_step (N draws per batch element in place of a beam) is sample_step.hip; the entry point below sends it there.
 // Every load address is clamped into its array and the value padded at use; no loop bound depends on
 // the data; a NaN anywhere can only change WHICH in-range index is written.
 // -ffp-contract=off: every score, key and lp is one separately rounded fp32 operation.
@@ -26,7 +27,7 @@
 namespace {
 
 using namespace beam_core;
-static_assert(sizeof(gpv_beam_args) == 144 && sizeof(gpv_beam_reorder_args) == 104, "ABI of include/gpv_beam.h");
+static_assert(sizeof(gpv_beam_args) == 176 && sizeof(gpv_beam_reorder_args) == 104, "ABI of include/gpv_beam.h");
 
 // The bitmaps of the constrained step, V bits each, lane-major: token v = it * LANES + lane is bit (it & 31) of word (it >> 5) * LANES + lane,
 // so a lane finds the bits of its own 32 next elements in ONE word (one LDS read per batch of UN loads, not one per element)
@@ -219,7 +220,10 @@ __global__ __launch_bounds__(256) void reorder_kernel(gpv_beam_reorder_args a, i
 
 extern "C" int gpv_beam_step(const gpv_beam_args* a, void* stream) {
   if (!check_step_common(a, a ? a->K : 1) || !a->finished) return (int)hipErrorInvalidValue;    // (K <= V: a row fills K list entries)
+  if (a->mode == GPV_BEAM_SAMPLE) return launch_sample(a, stream);                              // THE SAMPLER of the header: sample_step.hip
   if (a->mode != GPV_BEAM_EXTEND && a->mode != GPV_BEAM_FREEZE) return (int)hipErrorInvalidValue;
+  // the sampler's fields all zero is the step as it was; anything else in them is a caller's mistake
+  if (a->seed || a->cand_v || a->cand_w || a->top_k != 0 || a->inv_temp != 0.f || a->top_p != 0.f) return (int)hipErrorInvalidValue;
   // the constraints: all four fields zero is off; the penalty's factors are both zero or both finite and positive
   const bool rep_off = a->rep_neg == 0.f && a->rep_pos == 0.f;
   const bool rep_on = a->rep_neg > 0.f && a->rep_pos > 0.f && isfinite(a->rep_neg) && isfinite(a->rep_pos);

@@ -720,13 +720,14 @@ class GPV(nn.Module):
             inv_pen = tables[(T, alpha, str(dev))] = torch.from_numpy(rule.length_table(T, alpha)).to(dev)
         return inv_pen
 
-    def _device_steps(self, kv, T, parent, step):
+    def _device_steps(self, kv, T, parent, step, reorder=True):
         """the T - 1 steps of a device search: the decoder core, step(t, logits) (one launch; writes the next tokens straight into kv.tok
-        and the slots' parents into `parent`) and gpv_beam_reorder -- two launches per token beside the decoder's, no allocation"""
+        and the slots' parents into `parent`) and gpv_beam_reorder -- two launches per token beside the decoder's, no allocation.
+        reorder=False: every slot continues itself (a sampled step: the parent is the identity), so the caches stay where they are"""
         kv.tok.fill_(self.word_to_idx['__cls__'])
         for t in range(T - 1):
             step(t, kv._step_core(t))
-            if t + 1 < T - 1:                                                  # (nothing reads the caches after the last step)
+            if reorder and t + 1 < T - 1:                                      # (nothing reads the caches after the last step)
                 kv.reorder_device(parent, t + 1)
 
     def _beam_device(self, images, queries, beam_size, vocab_mask=None, impl='torch', finished='extend', alpha=0.0, constraints=None):
@@ -793,6 +794,91 @@ class GPV(nn.Module):
         mode, pad, stop = rule.MODES[finished], self.word_to_idx['__pad__'], self.word_to_idx['__stop__']
         self._device_steps(kv, T, parent, lambda t, logits: hip_beam.step(logits, lse, seq_lp, seqs, kv.tok, parent, fin, length, t, mode,
                                                                           pad, stop, inv_pen=inv_pen, vocab_mask=vocab_mask, **constraints))
+        outputs['_beam_seqs'], outputs['_beam_lp'] = seqs, seq_lp
+        outputs['beam_lengths'], outputs['beam_finished'] = length, fin
+        return outputs
+
+    def _sample_options(self, num_samples, temperature, top_k, top_p, vocab_mask, beam_options):
+        """the sampler's options of one call, checked before anything runs: the argument, else cfg['sample'], else temperature 1,
+        top_k = min(64, V), top_p off -> (N, (temperature, inv_temp) as Python floats or None, top_k, top_p as a Python float or None)"""
+        from . import beam as rule
+        given = sorted(k for k, v in beam_options.items() if v is not None)
+        if given:
+            known = ('beam_size', 'phrases', 'length_penalty', 'finished', 'impl', 'no_repeat_ngram', 'min_length', 'repetition_penalty')
+            if any(k not in known for k in given):
+                raise TypeError(f'forward_sample: unexpected argument(s) {[k for k in given if k not in known]}')
+            raise ValueError(f'forward_sample: {", ".join(given)} belong(s) to the beam search and do(es) not combine with sampling (a phrase set, '
+                             'a length penalty and the beam constraints with sampling are each a follow-up; the sampled step refuses them)')
+        sc = self.cfg.get('sample', None) or {}
+        temperature, top_k, top_p = (sc.get(k, None) if v is None else v for k, v in
+                                     zip(('temperature', 'top_k', 'top_p'), (temperature, top_k, top_p)))
+        V, T = len(self.vocab), self.cfg.max_text_len
+        if temperature is not None and not (math.isfinite(float(temperature)) and float(temperature) > 0.0):
+            raise ValueError(f'forward_sample: the temperature must be finite and positive, got {temperature!r} (use top_k=1 for the arg-max)')
+        inv_temp = rule.inv_temperature(temperature)
+        top_k = min(rule.MAX_C, V) if top_k is None else int(top_k)
+        top_p = None if top_p is None or float(top_p) in (0.0, 1.0) else float(rule.F32(top_p))
+        rule.check_sampler(int(num_samples), V, T, None, top_k, top_p, inv_temp)
+        if vocab_mask is not None and int(torch.isfinite(vocab_mask).sum()) < top_k:
+            raise ValueError(f'forward_sample: the vocabulary mask must leave at least top_k = {top_k} finite entries')
+        if self.training or torch.is_grad_enabled() or not self.cfg.get('kv_decode', True):
+            raise RuntimeError('forward_sample: sampling needs the KV-cached decoder (eval mode, no grad, cfg kv_decode); there is no fallback')
+        return int(num_samples), None if inv_temp is None else (float(temperature), float(inv_temp)), top_k, top_p
+
+    @torch.no_grad()
+    def forward_sample(self, images, queries, num_samples=1, temperature=None, top_k=None, top_p=None, seed=None, vocab_mask=None,
+                       **beam_options):
+        """num_samples answers per image, each drawn token by token on the device (hip_beam.sample_step: mode GPV_BEAM_SAMPLE of
+        gpv_beam_step; the rule: gpv1_amd.beam, THE SAMPLER): temperature, then the top_k largest logits (at most 64: sampling over the
+        whole vocabulary does not exist), then the nucleus top_p among them.  An argument that is None falls back to cfg['sample'], then to
+        temperature 1, top_k = min(64, V), top_p off.  seed: an int, or None for one value of torch's CPU generator (torch.manual_seed
+        makes a run repeatable).  A sample that emitted __stop__ is followed by __pad__ and keeps its score.
+        -> the usual outputs with 'answers' [B][N] words and 'answer_probs' [B][N], '_beam_seqs' [N,B,T], '_beam_lp' [B,N],
+        'beam_lengths', 'beam_finished'.  answer_probs / _beam_lp are the MODEL's probability of the sequence at that temperature over the
+        whole vocabulary, as the beam search reports it -- not the probability under the truncated sampler.
+        Eval mode, no grad and the KV-cached decoder only.  The arguments of the beam search (phrases, length_penalty, no_repeat_ngram,
+        min_length, repetition_penalty, beam_size ...) are refused."""
+        N, temp, top_k, top_p = self._sample_options(num_samples, temperature, top_k, top_p, vocab_mask, beam_options)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        from .misc import STAGER
+        dev = images.tensors.device if hasattr(images, 'tensors') else self.vision_token.device
+        seed_t = STAGER.to_device([seed - (1 << 64) if seed >= (1 << 63) else seed], torch.long, dev)     # the kernel reads the 64 bits
+        kw = dict(temperature=temp and temp[0], top_k=top_k, top_p=top_p)
+        outputs = None
+        if self.cfg.get('graph_inference', True):
+            queries = self._host_tokenize(images, queries)
+            # the seed travels as a static input of the graph: a replay with another seed samples anew
+            outputs = self._graphed(('sample', N, temp and temp[1], top_k, top_p),
+                                    lambda im, q, vm, sd: self._sample_device(im, q, N, sd, vocab_mask=vm, **kw), images, queries, vocab_mask,
+                                    extra=seed_t)
+        if outputs is None:
+            outputs = self._sample_device(images, queries, N, seed_t, vocab_mask=vocab_mask, **kw)
+        keep = {k: outputs[k] for k in ('_beam_seqs', '_beam_lp')}
+        outputs = self._beam_answers(outputs)
+        outputs.update(keep)
+        return outputs
+
+    def _sample_device(self, images, queries, N, seed, vocab_mask=None, temperature=None, top_k=1, top_p=None):
+        """device part of the sampled search: per token the decoder core and ONE launch (the parent is the identity: no cache reorder)"""
+        from . import hip_beam
+        outputs, memory = self._encode(images, queries, self._bert_fork(images, queries) if self._capturing(images, queries) else None)
+        B, K, T = memory.shape[0], N, self.cfg.max_text_len
+        dev = memory.device
+        kv = self._beam_kv(memory, K)
+        if vocab_mask is not None:
+            vocab_mask = vocab_mask.to(device=dev, dtype=torch.float32).contiguous()
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+        seq_lp = torch.zeros(B, K, device=dev)
+        seqs = torch.zeros(K, B, T, dtype=torch.long, device=dev)
+        lse, cand_w, cand_v = torch.zeros(K * B, device=dev), torch.zeros(K * B, top_k, device=dev), i32(K * B, top_k)
+        parent, fin, length = i32(B, K), i32(B, K), i32(B, K)
+        pad, stop = self.word_to_idx['__pad__'], self.word_to_idx['__stop__']
+        self._device_steps(kv, T, parent, lambda t, logits: hip_beam.sample_step(logits, lse, seq_lp, seqs, kv.tok, parent, fin, length, t, pad,
+                                                                                 stop, seed, cand_v, cand_w, top_k, top_p=top_p,
+                                                                                 temperature=temperature, vocab_mask=vocab_mask),
+                           reorder=False)
         outputs['_beam_seqs'], outputs['_beam_lp'] = seqs, seq_lp
         outputs['beam_lengths'], outputs['beam_finished'] = length, fin
         return outputs

@@ -1,7 +1,8 @@
-"""ctypes binding of libgpv_beam.so (C ABI in include/gpv_beam.h): the beam search step and the KV-cache reorder on the device.
+"""ctypes binding of libgpv_beam.so (C ABI in include/gpv_beam.h): the beam search step, the sampled step (one more mode of the same
+entry point) and the KV-cache reorder on the device.
 
 Same rules as ``hip``: no CPU / eager fallback -- a missing library or a CPU tensor is an error.  Nothing here synchronises or
-allocates: both calls are capturable.  The rule is stated in ``gpv1_amd.beam``.
+allocates: all three calls are capturable.  The rule is stated in ``gpv1_amd.beam``.
 """
 import ctypes as C
 from functools import partial
@@ -23,9 +24,11 @@ _want = partial(_native.want, 'hip_beam')
 class BeamArgs(C.Structure):
     _fields_ = [('logits', C.c_void_p), ('pitch', C.c_int64), ('vocab_mask', C.c_void_p), ('inv_pen', C.c_void_p), ('lse', C.c_void_p),
                 ('seq_lp', C.c_void_p), ('seqs', C.c_void_p), ('tok', C.c_void_p), ('parent', C.c_void_p), ('finished', C.c_void_p),
-                ('length', C.c_void_p), ('B', C.c_int), ('K', C.c_int), ('V', C.c_int), ('T', C.c_int), ('t', C.c_int),
-                ('mode', C.c_int), ('pad_id', C.c_int), ('stop_id', C.c_int), ('dtype', C.c_int), ('no_repeat', C.c_int),
-                ('min_len', C.c_int), ('rep_neg', C.c_float), ('rep_pos', C.c_float)]
+                ('length', C.c_void_p), ('seed', C.c_void_p), ('cand_v', C.c_void_p), ('cand_w', C.c_void_p),
+                ('B', C.c_int), ('K', C.c_int), ('V', C.c_int), ('T', C.c_int), ('t', C.c_int),
+                ('mode', C.c_int), ('pad_id', C.c_int), ('stop_id', C.c_int), ('dtype', C.c_int),
+                ('top_k', C.c_int), ('inv_temp', C.c_float), ('top_p', C.c_float),         # (the sampler's; the constraints' stay the last four)
+                ('no_repeat', C.c_int), ('min_len', C.c_int), ('rep_neg', C.c_float), ('rep_pos', C.c_float)]
 
 
 class ReorderArgs(C.Structure):
@@ -88,6 +91,27 @@ def step(logits, lse, seq_lp, seqs, tok, parent, finished, length, t, mode, pad_
     a = BeamArgs(vocab_mask=None if vocab_mask is None else _want('vocab_mask', vocab_mask, torch.float32, (V,)),
                  finished=_want('finished', finished, torch.int32, (B, K)), t=t, mode=mode, pad_id=pad_id, stop_id=stop_id,
                  no_repeat=int(no_repeat_ngram), min_len=int(min_length), rep_neg=float(rep_neg), rep_pos=float(rep_pos), **f)
+    _chk(lib().gpv_beam_step(C.byref(a), _stream()), 'gpv_beam_step')
+
+
+def sample_step(logits, lse, seq_lp, seqs, tok, parent, finished, length, t, pad_id, stop_id, seed, cand_v, cand_w, top_k, top_p=None,
+                temperature=None, vocab_mask=None):
+    """gpv_beam_step in mode GPV_BEAM_SAMPLE on the current stream (THE SAMPLER of gpv1_amd.beam): one launch, no sync, everything in
+    place.  The tensors of `step`, the K slots being the K samples of a batch element; seed: ONE int64 on the device, read by the kernel
+    (rewrite it between the replays of a captured search); cand_v [K*B, top_k] int32 and cand_w [K*B, top_k] fp32 out (the candidates by
+    rank and expf of their log-probabilities); top_p None: off; temperature None: 1.  parent comes back as the identity: no reorder
+    follows.  seq_lp is the model's log-probability of the sequence at that temperature, not the truncated sampler's."""
+    inv_temp = rule.inv_temperature(temperature)
+    f, K, B, T, V = step_fields('hip_beam', logits, lse, seq_lp, seqs, tok, parent, length, None,
+                                lambda K, V, T: rule.check_sampler(K, V, T, t, top_k, top_p, inv_temp))
+    if not (0 <= pad_id < V and 0 <= stop_id < V):
+        raise ValueError(f'hip_beam.sample_step: pad_id / stop_id must lie in the vocabulary, got {pad_id} / {stop_id} of {V}')
+    C_ = int(top_k)
+    a = BeamArgs(vocab_mask=None if vocab_mask is None else _want('vocab_mask', vocab_mask, torch.float32, (V,)),
+                 finished=_want('finished', finished, torch.int32, (B, K)), t=t, mode=rule.SAMPLE, pad_id=pad_id, stop_id=stop_id,
+                 seed=_want('seed', seed, torch.int64, (1,)), cand_v=_want('cand_v', cand_v, torch.int32, (K * B, C_)),
+                 cand_w=_want('cand_w', cand_w, torch.float32, (K * B, C_)), top_k=C_, inv_temp=0.0 if inv_temp is None else float(inv_temp),
+                 top_p=0.0 if top_p is None else float(rule.F32(top_p)), **f)
     _chk(lib().gpv_beam_step(C.byref(a), _stream()), 'gpv_beam_step')
 
 

@@ -13,6 +13,7 @@ usage: python -m gpv1_amd.inference [--config some.yaml] ckpt=... inputs.img=img
                                       [beam_size=5] [num_output_boxes=5]
                                       [beam.impl=device] [beam.finished=freeze] [beam.length_penalty=0.6]
                                       [inputs.answers="cat|dog|traffic light"]
+                                      [sample.num=3] [sample.temperature=0.8] [sample.top_k=20] [sample.top_p=0.9] [sample.seed=1]
                                       [outputs.vis=picture.jpg]
 ``outputs.vis`` (the reference's ``inference_util.vis_sample``): the picture the model saw with the ``num_output_boxes`` boxes drawn,
 encoded on the device (gpv1_amd.jpeg_encode.DeviceJpegEncoder) and written to that path.
@@ -127,14 +128,26 @@ def beam_options(beam):
 
 
 @torch.no_grad()
-def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=None, beam=None, answers=None):
+def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=None, beam=None, answers=None, sample=None):
     """images: list of arrays/tensors (see preprocess_image); queries: list[str] or (ids, mask) tensors;
     size: (H, W) to resize HxWx3 arrays to first (the data loader's 480x640), None = as they are (inference.py).  Any image size
     runs: the batch is padded to its largest image and the encoder attends over ceil(H / 32) ceil(W / 32) tokens (850 for
     800x1088), beyond 320 of them on the streaming attention kernels.  answers (added): a list of answer texts -- the answer is one of
     them (phrases.PhraseSet, GPV.forward_beam_search with phrases=, beam_size default min(4, len(answers))): 'answer' is the chosen
-    text, 'answer_log_prob' the model's log-probability of it followed by __stop__, 'runners_up' the other slots' (text, log_prob)"""
+    text, 'answer_log_prob' the model's log-probability of it followed by __stop__, 'runners_up' the other slots' (text, log_prob).
+    sample (added): the `sample` group of a config (num, temperature, top_k, top_p, seed) -- `num` answers drawn by GPV.forward_sample:
+    'answer' / 'answer_prob' are the first draw's, 'samples' all of them as (text, probability the model gives the sequence)"""
     dev = model.vision_token.device
+    if sample:
+        # refused before anything runs: a draw is not a search, and a closed answer set is not taught to the sampled step
+        if beam_size and int(beam_size) > 1:
+            raise ValueError(f'predict: sample and beam_size={beam_size} exclude each other (sampling draws its answers, a beam search '
+                             'ranks them: ask for one of the two)')
+        if answers:
+            raise ValueError('predict: sample and answers exclude each other (sampling inside a phrase set is a follow-up: the sampled '
+                             'step does not walk the trie)')
+        if beam_options(beam):
+            raise ValueError(f'predict: sample and the beam options {sorted(beam_options(beam))} exclude each other (they steer the beam search)')
     if size is not None:
         images = [resize_image(i, size) if not torch.is_tensor(i) else i for i in images]
     imgs = nested_tensor_from_tensor_list([preprocess_image(i).to(dev) for i in images])
@@ -149,6 +162,13 @@ def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=
         for b, d in enumerate(decoded):
             ranked = [(answers[p], l) for p, l in zip(phrase[b], lp[b]) if p >= 0]
             d['answer'], d['answer_log_prob'], d['runners_up'] = ranked[0][0], ranked[0][1], ranked[1:]
+        return decoded
+    if sample:
+        out = model.forward_sample(imgs, queries, num_samples=int(sample.get('num', None) or 1), temperature=sample.get('temperature', None),
+                                   top_k=sample.get('top_k', None), top_p=sample.get('top_p', None), seed=sample.get('seed', None))
+        decoded = decode_outputs(out, model, num_output_boxes)
+        for b, d in enumerate(decoded):
+            d['samples'] = [(detokenize(words), p) for words, p in zip(out['answers'][b], out['answer_probs'][b])]
         return decoded
     if beam_size:
         out = model.forward_beam_search(imgs, queries, beam_size=beam_size, **beam_options(beam))
@@ -175,14 +195,16 @@ def main(argv=None):
     ap.add_argument('overrides', nargs='*')
     args = ap.parse_args(argv)
     # outputs.vis= ckpt= inputs.img= inputs.query= inputs.answers= beam_size= beam.impl= beam.finished= beam.length_penalty=
-    # beam.no_repeat_ngram= beam.min_length= beam.repetition_penalty= are added keys
+    # beam.no_repeat_ngram= beam.min_length= beam.repetition_penalty= sample.num= sample.temperature= sample.top_k= sample.top_p=
+    # sample.seed= are added keys
     cfg = load_config(args.config, args.overrides, strict=False) if args.config else from_dict(default_tree(), args.overrides, strict=False)
     model = GPV(cfg.model).cuda().eval()
     load_model_state(model, cfg.get('ckpt', cfg.eval.ckpt), map_location='cuda:0')
     img = np.load(cfg.inputs.img)
     answers = cfg.inputs.get('answers', None)                    # inputs.answers="cat|dog|traffic light": the answer is one of these
     pred = predict(model, [img], [cfg.inputs.query], beam_size=cfg.get('beam_size'), num_output_boxes=cfg.get('num_output_boxes', 5),
-                   beam=cfg.get('beam'), answers=[a.strip() for a in str(answers).split('|') if a.strip()] if answers else None)[0]
+                   beam=cfg.get('beam'), answers=[a.strip() for a in str(answers).split('|') if a.strip()] if answers else None,
+                   sample=cfg.get('sample'))[0]
     for k, v in pred.items():
         print('-' * 80)
         print(k)

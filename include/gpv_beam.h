@@ -47,6 +47,31 @@
  * 0 <= min_len <= T, rep_neg and rep_pos both zero or both finite and positive, and with any constraint on V <= GPV_BEAM_MAX_CONSTR_V
  * (a "seen" and a "banned" bitmap of V bits each in LDS, 16 KB together).
  *
+ * THE SAMPLER (mode GPV_BEAM_SAMPLE: N draws per batch element in place of a beam).  Step t, batch element b, slot k = 0..K-1: the slots
+ * are the N samples of b, so N = K <= GPV_BEAM_MAX_K; logits row r = k*B + b.  lse, cand_v and cand_w are written for every row, finished
+ * or not.
+ *  1. Temperature and mask.  x_v = fp32(logit[r, v]) * inv_temp: one fp32 multiply; inv_temp = fp32(1 / temperature), computed in
+ *     float64 on the host; field value 0 means temperature 1: no multiply.  Then + vocab_mask[v]: one fp32 add; no add when the mask
+ *     is absent.
+ *  2. Normalisation.  m and lse_r are taken over all v of the row as it stands after step 1, in the summation order pinned below.  lse
+ *     is an OUTPUT of the device and an INPUT of the host rule.
+ *  3. Candidates: the C = top_k largest x_v, ties to the lower v, rank j = 0..C-1; 1 <= C <= GPV_BEAM_MAX_C, C <= V.
+ *     lp_j = x_j - lse_r: one fp32 subtract.  w_j = expf(lp_j) is evaluated on the device only.  cand_v[r, j] (int32) and cand_w[r, j]
+ *     (fp32), both [K*B, C], are OUTPUTS of the step; cand_w is an INPUT of the host rule, which recomputes cand_v and lp itself.
+ *  4. Nucleus.  c_j = c_{j-1} + w_j, c_{-1} = 0: serial fp32 additions in rank order.  n = 1 + #{ j in 0..C-2 : c_j < top_p }.  Field
+ *     value 0 means off: n = C.  Otherwise 0 < top_p < 1.
+ *  5. Draw.  bits = hash_u32(seed, ((uint64) t * B + b) * K + k), the function of csrc/common.h.  seed is read from a DEVICE pointer
+ *     that holds one value: the caller rewrites it between replays, so a captured search draws anew each time.
+ *     u = fp32(bits >> 8) * 2^-24, which is exact.  tau = u * c_{n-1}: one fp32 multiply.  j* = the first j < n with c_j > tau; if there
+ *     is none, j* = n - 1.
+ *  6. Finished slots behave as FREEZE does: with finished[b,k] set the token is pad_id, seq_lp and length stay unchanged.
+ *  7. Write.  parent[b,k] = k.  seq_lp'[b,k] = seq_lp[b,k] + lp_{j*}: one fp32 add.  seqs'[k,b,t] = tok[k*B+b] = cand_v[r, j*].
+ *     length' = length + 1.  finished' = finished | (token == stop_id).  No -1e9 rule at t = 0: the K slots differ by their draw.
+ * Caller conditions: a mask leaves at least C finite entries per row; inv_pen, no_repeat, min_len and rep_* must be off in this mode
+ * and are refused otherwise.  The reported seq_lp is the model's log-probability of the sequence at that temperature, over the whole
+ * vocabulary -- what the beam search reports -- not the probability under the truncated sampler.  The sampler is truncated to at most
+ * GPV_BEAM_MAX_C candidates; pure sampling over all of V does not exist.
+ *
  * THE SUM OF STEP 2.  256 lanes; lane l adds expf(x_v - m) for v = l, l + 256, l + 512, ... in ascending v onto 0.f, the 64 lanes
  * of a wave are folded by xor butterflies (32, 16, 8, 4, 2, 1), the four wave sums are added one after the other in wave order.
  * The longest chain of dependent fp32 additions is therefore  n_chain(V) = ceil(V / 256) + 6 + 3. */
@@ -63,9 +88,11 @@ extern "C" {
 #define GPV_BEAM_LANES 256      /* threads of a gpv_beam_step workgroup: the stride of the sum of step 2 */
 #define GPV_BEAM_MAX_NGRAM 8    /* largest no_repeat */
 #define GPV_BEAM_MAX_CONSTR_V 65536   /* largest V with a constraint on */
+#define GPV_BEAM_MAX_C 64       /* largest top_k of the sampler */
 
 #define GPV_BEAM_EXTEND 0       /* finished hypotheses keep extending (the reference) */
 #define GPV_BEAM_FREEZE 1       /* a hypothesis that emitted stop_id keeps its score and is followed by pad_id */
+#define GPV_BEAM_SAMPLE 2       /* THE SAMPLER: every slot draws its own next token; finished slots as in FREEZE */
 
 #define GPV_BEAM_BF16 0         /* dtype codes, the values of GPV_BF16 / GPV_F32 in gpv_hip.h */
 #define GPV_BEAM_F32 1
@@ -82,10 +109,16 @@ typedef struct gpv_beam_args {
   int* parent;                  /* [B,K] out */
   int* finished;                /* [B,K] in / out, 0 or 1 */
   int* length;                  /* [B,K] in / out */
+  const uint64_t* seed;         /* the sampler's seed: ONE value in device memory, read by the kernel; NULL in the other modes */
+  int* cand_v;                  /* [K*B, top_k] out, the sampler's candidates by rank; NULL in the other modes */
+  float* cand_w;                /* [K*B, top_k] out, expf(lp) of the candidates; NULL in the other modes */
   int B, K, V, T, t;
-  int mode;                     /* GPV_BEAM_EXTEND / GPV_BEAM_FREEZE */
+  int mode;                     /* GPV_BEAM_EXTEND / GPV_BEAM_FREEZE / GPV_BEAM_SAMPLE */
   int pad_id, stop_id;          /* in [0, V) */
   int dtype;                    /* of logits: GPV_BEAM_BF16 / GPV_BEAM_F32 */
+  int top_k;                    /* the sampler's C, 1 .. GPV_BEAM_MAX_C; 0 in the other modes */
+  float inv_temp;               /* the sampler's step 1: fp32(1 / temperature); 0 = temperature 1 */
+  float top_p;                  /* the sampler's step 4: 0 < top_p < 1; 0 = off */
   int no_repeat;                /* n of step 3a (i): no n-gram is written twice; 0 = off */
   int min_len;                  /* step 3a (ii): stop_id is banned while length < min_len; 0 = off */
   float rep_neg, rep_pos;       /* step 1b: fp32(theta), fp32(1 / theta); both 0 = off */
@@ -98,7 +131,13 @@ typedef struct gpv_beam_args {
  * Every load is from a clamped index and padded at use.  B = 0: nothing is launched.
  * With a constraint on, another instantiation runs: per row the workgroup marks the history's tokens in the seen bitmap and the row's
  * bans in the banned bitmap (LDS; the words it touched are zeroed again behind the row), applies 1b at every load of both passes, keeps
- * banned tokens out of the lane lists and reduces m over the whole row.  Still one launch. */
+ * banned tokens out of the lane lists and reduces m over the whole row.  Still one launch.
+ * Mode GPV_BEAM_SAMPLE (csrc/sample_step.hip): per row top_k pops; a lane's list holds eight entries, and when the owner of a pop has
+ * used up its eight every lane rebuilds its list from the elements that come strictly behind the last popped (x, v) in the order "x
+ * descending, v ascending" -- one scan of the row when the candidates are spread over the lanes, at most ceil(top_k / 8) -- and the sum pass;
+ * thread k then does steps 4 - 7 of slot k on the at most 64 values of its row in LDS.  Still one launch; parent is the identity, so no
+ * gpv_beam_reorder follows.  The sampler's fields (seed, cand_v, cand_w, top_k, inv_temp, top_p) all zero with mode EXTEND or FREEZE is
+ * the step as it was; anything else in them is refused there.  They stand in front of the constraints' fields, which stay the last four. */
 int gpv_beam_step(const gpv_beam_args* a, void* stream);
 
 typedef struct gpv_beam_reorder_args {

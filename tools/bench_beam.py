@@ -3,6 +3,7 @@
 
   python tools/bench_beam.py [--out profiles/r13_beam.txt] [--passes 5] [--reps 3] [--no-trace]
                              [--no-repeat N] [--min-length M] [--repetition-penalty THETA]
+                             [--sample N --top-k C [--top-p P]]
 
 The two paths alternate in one process, `--passes` passes of `--reps` searches each (per-search wall time incl. the host detokenisation,
 as bench.py times it); median and min - max of the passes are reported.  Then ONE `rocprofv3 --kernel-trace` run of a fresh child process
@@ -15,7 +16,9 @@ T - 1 decoder cores are taken off.
 
 A last section times gpv_beam_step alone with device events at the search's shapes (B = 64, K = 5, the model's vocabulary, bf16 logits
 of pitch T*V, the longest history t = T - 2).  --no-repeat / --min-length / --repetition-penalty (the constraints of gpv1_amd.beam) add
-a third path to the alternation, the device path with these options, and to that section each given option alone and all together."""
+a third path to the alternation, the device path with these options, and to that section each given option alone and all together.
+--sample N --top-k C [--top-p P] adds the sampled search (GPV.forward_sample: N draws per image, no reorder launches) to the alternation
+and the sampled step alone (mode GPV_BEAM_SAMPLE, K = N) at C in {8, 20, 64} and the given C to that section."""
 import argparse
 import csv
 import glob
@@ -125,8 +128,36 @@ def step_times(torch, V, T, variants, runs=7, launches=200):
     return {name: ts[1:] for name, ts in out.items()}
 
 
+def sample_step_times(torch, V, T, N, Cs, top_p, runs=7, launches=200):
+    """the sampled step alone at the search's shapes (B = BATCH, K = N), device events around `launches` launches -> {C: [us per launch]}"""
+    import gpv1_amd.hip_beam as hip_beam
+    dev = torch.device('cuda:0')
+    g = torch.Generator(device='cpu').manual_seed(0)
+    t = T - 2
+    buf = (3.0 * torch.randn(N * BATCH, T, V, generator=g)).to(torch.bfloat16).to(dev)
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    seed = torch.tensor([1], dtype=torch.long, device=dev)
+    out = {c: [] for c in Cs}
+    for _ in range(runs + 1):                                                # (the first round is the warm-up)
+        for c in Cs:
+            seq_lp, seqs, lse = torch.zeros(BATCH, N, device=dev), torch.zeros(N, BATCH, T, dtype=torch.long, device=dev), torch.zeros(N * BATCH, device=dev)
+            tok, parent, fin, length = torch.zeros(N * BATCH, dtype=torch.long, device=dev), i32(BATCH, N), i32(BATCH, N), i32(BATCH, N) + t
+            cand_v, cand_w = i32(N * BATCH, c), torch.zeros(N * BATCH, c, device=dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(launches):
+                hip_beam.sample_step(buf[:, t], lse, seq_lp, seqs, tok, parent, fin, length, t, V - 4, V - 2, seed, cand_v, cand_w, c, top_p=top_p)
+            e1.record()
+            torch.cuda.synchronize()
+            out[c].append(e0.elapsed_time(e1) / launches * 1e3)
+    return {c: ts[1:] for c, ts in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--sample', type=int, default=0, help='N: add the sampled search of N draws per image (GPV.forward_sample)')
+    ap.add_argument('--top-k', type=int, default=20, help='top_k of the sampled search')
+    ap.add_argument('--top-p', type=float, default=None, help='top_p of the sampled search')
     ap.add_argument('--no-repeat', type=int, default=0, help='no_repeat_ngram of the constrained path')
     ap.add_argument('--min-length', type=int, default=0, help='min_length of the constrained path')
     ap.add_argument('--repetition-penalty', type=float, default=None, help='repetition_penalty of the constrained path')
@@ -146,11 +177,24 @@ def main():
     paths = {'torch': dict(impl='torch'), 'device': dict(impl='device')}
     if constr:
         times['constrained'], paths['constrained'] = [], dict(impl='device', **constr)
+    search = lambda impl: model.forward_beam_search(samples, q, beam_size=K, **paths[impl])
+    if args.sample:
+        times['sampled'] = []
+        if args.sample != K:                                                 # the beam search of the same K, to set the sampled search against
+            times[f'device K={args.sample}'] = []
+        beam = search
+
+        def search(impl):
+            if impl == 'sampled':
+                return model.forward_sample(samples, q, num_samples=args.sample, top_k=args.top_k, top_p=args.top_p, seed=1)
+            if impl.startswith('device K='):
+                return model.forward_beam_search(samples, q, beam_size=args.sample, impl='device')
+            return beam(impl)
     with torch.no_grad():
         outs = {}
         for impl in times:                                                   # warm-up + capture of the graphs
             for _ in range(2):
-                outs[impl] = model.forward_beam_search(samples, q, beam_size=K, **paths[impl])
+                outs[impl] = search(impl)
         torch.cuda.synchronize()
         same = sum(a == b for x, y in zip(outs['torch']['answers'], outs['device']['answers']) for a, b in zip(x, y))
         for _ in range(args.passes):
@@ -158,7 +202,7 @@ def main():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(args.reps):
-                    model.forward_beam_search(samples, q, beam_size=K, **paths[impl])
+                    search(impl)
                 torch.cuda.synchronize()
                 times[impl].append((time.perf_counter() - t0) / args.reps * 1e3)
     lines = [f'# tools/bench_beam.py: forward_beam_search(beam_size={K}) of {BATCH} synthetic 480x640 images, bf16, V = {len(model.vocab)}, T = {T}, the whole search one hipGraph',
@@ -179,6 +223,13 @@ def main():
     step_lines = [f'gpv_beam_step alone (B = {BATCH}, K = {K}, V = {V}, bf16, pitch T*V, t = T - 2 = {T - 2}; device events, 7 runs of 200 launches, us per launch):']
     for name, ts in step_times(torch, V, T, variants).items():
         step_lines.append(f'  {name:24s} median {statistics.median(ts):.2f}   min {min(ts):.2f}   max {max(ts):.2f}')
+    if args.sample:
+        lines.insert(2, f'# sampled = forward_sample(num_samples={args.sample}, top_k={args.top_k}, top_p={args.top_p}): the sampled step, no reorder launches')
+        Cs = sorted({8, 20, 64, args.top_k})
+        step_lines.append(f'gpv_beam_step in mode SAMPLE alone (B = {BATCH}, K = N = {args.sample}, V = {V}, bf16, pitch T*V, top_p = {args.top_p}; us per launch; '
+                          'C pops, 1 .. ceil(C / 8) scans of the row -- random logits: 1 -- and the sum pass, finished slots included):')
+        for c, ts in sample_step_times(torch, V, T, args.sample, Cs, args.top_p).items():
+            step_lines.append(f'  top_k = {c:<3d}                 median {statistics.median(ts):.2f}   min {min(ts):.2f}   max {max(ts):.2f}')
     spread = max(max(ts) - min(ts) for ts in times.values())
     d = statistics.median(times['device']) - statistics.median(times['torch'])
     lines.append(f'device - torch = {d:+.3f} ms (largest min - max spread of a path in this run: {spread:.3f} ms): '
