@@ -1,5 +1,5 @@
 // libgpv_enc.so (include/gpv_enc.h): a batch of pictures encoded as baseline JPEG files on the device.  The arithmetic of the rule
-// (colour, sampling, transform, quantiser, entropy code of a block, box corners, denormalise) is jpeg_enc_host.h, compiled here for
+// (colour, sampling, transform, quantiser, entropy code of a block, box corners, labels, denormalise) is jpeg_enc_host.h, compiled here for
 // the device as it stands; this file adds the four kernels around it and the entry points.  Built with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,7 +10,7 @@
 
 namespace R = gpv_enc_rule;
 
-static_assert(GPV_ENC_HEADER_BYTES == R::HEADER_BYTES && GPV_ENC_MAX_BOXES == R::MAX_BOXES, "header constants");
+static_assert(GPV_ENC_HEADER_BYTES == R::HEADER_BYTES && GPV_ENC_MAX_BOXES == R::MAX_BOXES && GPV_ENC_MAX_LABEL == R::MAX_LABEL, "header constants");
 static_assert(GPV_ENC_BLOCK_BYTES * 8 >= R::MAX_BLOCK_BITS && GPV_ENC_BLOCK_BYTES % 16 == 0, "packed bytes per block");
 static_assert(sizeof(gpv_enc_desc) == 80, "descriptor size (workspace formula)");
 static_assert((int64_t)GPV_ENC_MAX_BLOCKS * GPV_ENC_BLOCK_BYTES * 8 < ((int64_t)1 << 31), "bit offsets are 32-bit");
@@ -18,6 +18,7 @@ static_assert((int64_t)GPV_ENC_MAX_BLOCKS * GPV_ENC_BLOCK_BYTES * 8 < ((int64_t)
 namespace {
 
 __constant__ const R::Tables d_T = R::make_tables();
+__constant__ const R::LabelFont d_font = R::make_label_font();
 constexpr R::Tables h_T = R::make_tables();
 
 constexpr int COEF_THREADS = 256, ROW = COEF_THREADS + 2;     // LDS row of one zigzag position: + 2 keeps the transposed read off one bank
@@ -54,12 +55,23 @@ struct LdsColumn {                       // one thread's 64 values, one per LDS 
   __device__ int16_t& operator[](int k) const { return base[k * ROW]; }
 };
 
-struct Pixels {                          // component `comp` of the pixel at (x, y), the box outlines drawn over the source
+struct LabelStage {                      // what the workgroup stages of its picture's labels (LDS)
+  R::Label label[R::MAX_BOXES];
+  uint8_t glyph[R::MAX_BOXES * R::MAX_LABEL];   // glyph_of of every text byte
+  R::LabelFont font;
+};
+
+// component `comp` of the pixel at (x, y), the box outlines drawn over the source and, with LABELS, the labels over the outlines.
+// touched: bit n = the plate of box n reaches the footprint of the thread's block (labels_touching); others are not looked at.
+template <bool LABELS>
+struct Pixels {
   const void* src;
   int pitch, kind, nbox;
   float mean[3], std[3];
   const int (*rect)[4];
   const uint8_t (*colour)[4];
+  const LabelStage* stage;
+  uint32_t touched;
   __device__ int operator()(int x, int y, int comp) const {
     int64_t i = (int64_t)y * pitch + x;
     int r, g, b;
@@ -79,12 +91,40 @@ struct Pixels {                          // component `comp` of the pixel at (x,
     }
     for (int n = 0; n < nbox; ++n)
       if (R::on_outline(rect[n], x, y)) r = colour[n][0], g = colour[n][1], b = colour[n][2];
+    if constexpr (LABELS) {
+      int last = -1;                                         // a later label overwrites an earlier one: only the last one shows
+      for (uint32_t m = touched; m; m &= m - 1) {
+        const int n = __builtin_ctz(m);
+        if (R::on_plate(stage->label[n], x, y)) last = n;
+      }
+      if (last >= 0) {
+        const bool ink = R::label_ink(stage->label[last], stage->font, stage->glyph, x, y);
+        r = ink ? colour[last][0] : R::PLATE_RGB, g = ink ? colour[last][1] : R::PLATE_RGB, b = ink ? colour[last][2] : R::PLATE_RGB;
+      }
+    }
     return R::ycc(comp, r, g, b);
   }
 };
 
+// the plates that reach the source pixels block b samples: 8 x 8 for a full-resolution component, 8 hs x 8 vs for down-sampled
+// chroma, the clamps of sample_block applied to both ends (they are monotone, so no sampled pixel lies outside)
+__device__ inline uint32_t labels_touching(const LabelStage& st, int nbox, const R::Geometry& g, const R::Block& b, int H, int W) {
+  const bool full = b.comp == 0 || (g.hs == 1 && g.vs == 1);
+  const int sx = full ? 1 : 2, sy = full ? 1 : g.vs;
+  int x0 = b.bx * 8 * sx, x1 = x0 + 8 * sx - 1, y0 = b.by * 8 * sy, y1 = y0 + 8 * sy - 1;
+  x0 = x0 < W - 1 ? x0 : W - 1, x1 = x1 < W - 1 ? x1 : W - 1, y0 = y0 < H - 1 ? y0 : H - 1, y1 = y1 < H - 1 ? y1 : H - 1;
+  uint32_t m = 0;
+  for (int n = 0; n < nbox; ++n) {
+    const R::Label& l = st.label[n];
+    if (l.n > 0 && l.px <= x1 && l.px + R::CELL_W * l.n + 2 > x0 && l.py <= y1 && l.py + R::PLATE_H > y0) m |= 1u << n;
+  }
+  return m;
+}
+
 // 1. pixels -> quantised coefficients in zigzag order and the bit count of each block's AC code.  grid (blocks of the largest
 // picture / 256, B); a thread whose block index is beyond its picture's count only helps with the barriers.
+// LABELS (a compile-time tag: without it this is the kernel as it was): the pictures' labels are staged and drawn as well.
+template <bool LABELS>
 __global__ __launch_bounds__(COEF_THREADS) void gpv_enc_coef_kernel(char* ws, int B, int64_t blocks, R::Quant Q, int hs, int vs) {
   __shared__ int16_t s_zz[64 * ROW];
   __shared__ int s_rect[R::MAX_BOXES][4];
@@ -99,6 +139,24 @@ __global__ __launch_bounds__(COEF_THREADS) void gpv_enc_coef_kernel(char* ws, in
     for (int c = 0; c < 4; ++c) s_colour[tid][c] = D.colours[4 * tid + c];
   }
   __syncthreads();
+  const LabelStage* stage = nullptr;
+  if constexpr (LABELS) {
+    __shared__ LabelStage st;
+    stage = &st;
+    // the extents the host has checked, clamped again: no index below leaves colours[0 .. 4 nbox + nlab) or the glyph table
+    const int most = nbox * R::MAX_LABEL, nlab = D.labels < 0 ? 0 : D.labels > most ? most : D.labels;
+    if (tid == 0) {                                          // at most 32 boxes: a serial prefix sum over the length bytes
+      int before = 0;
+      for (int n = 0; n < nbox; ++n) {
+        st.label[n] = R::label_place(s_rect[n], s_colour[n][3], before, nlab, D.H, D.W);
+        before += s_colour[n][3] & 0x7F;
+      }
+    }
+    for (int i = tid; i < nlab; i += COEF_THREADS) st.glyph[i] = (uint8_t)R::glyph_of(D.colours[4 * nbox + i]);
+    if (nlab > 0)                                            // (a picture without labels in a call that has some: every n is 0)
+      for (int i = tid; i < (int)sizeof(R::LabelFont); i += COEF_THREADS) ((uint8_t*)&st.font)[i] = ((const uint8_t*)&d_font)[i];
+    __syncthreads();
+  }
   const R::Geometry g = R::geometry(D.H, D.W, hs, vs);
   LdsColumn col{s_zz + tid};
   int acbits = 0;
@@ -108,7 +166,8 @@ __global__ __launch_bounds__(COEF_THREADS) void gpv_enc_coef_kernel(char* ws, in
     if (b.dummy) {
       for (int i = 0; i < 64; ++i) col[i] = 0;
     } else {
-      Pixels px{D.src, D.pitch, D.kind, nbox, {D.mean[0], D.mean[1], D.mean[2]}, {D.std[0], D.std[1], D.std[2]}, s_rect, s_colour};
+      Pixels<LABELS> px{D.src, D.pitch, D.kind, nbox, {D.mean[0], D.mean[1], D.mean[2]}, {D.std[0], D.std[1], D.std[2]}, s_rect, s_colour, stage, 0};
+      if constexpr (LABELS) px.touched = labels_touching(*stage, nbox, g, b, D.H, D.W);
       R::sample_block(px, g, b, D.H, D.W, col);
       int d[64];
 #pragma unroll
@@ -331,12 +390,15 @@ int gpv_enc_encode(gpv_enc_desc* descs, int B, int quality, int subsampling, voi
     return hipErrorInvalidValue;
   int64_t blocks = 0;
   int largest = 0;
+  bool labelled = false;
   for (int i = 0; i < B; ++i) {
     gpv_enc_desc& d = descs[i];
     if (d.H < 1 || d.H > 65535 || d.W < 1 || d.W > 65535 || d.pitch < d.W || !d.src || d.nboxes < 0 || d.nboxes > GPV_ENC_MAX_BOXES ||
         (d.nboxes && (!d.boxes || !d.colours)) || d.kind < GPV_ENC_SRC_U8 || d.kind > GPV_ENC_SRC_F32 ||
-        (d.kind == GPV_ENC_SRC_BF16 && ((uintptr_t)d.src & 7)) || (d.kind == GPV_ENC_SRC_F32 && ((uintptr_t)d.src & 15)))
+        (d.kind == GPV_ENC_SRC_BF16 && ((uintptr_t)d.src & 7)) || (d.kind == GPV_ENC_SRC_F32 && ((uintptr_t)d.src & 15)) ||
+        d.labels < 0 || d.labels > d.nboxes * GPV_ENC_MAX_LABEL)     // (labels > 0 with no boxes is the second one)
       return hipErrorInvalidValue;
+    labelled |= d.labels > 0;
     int64_t n = (int64_t)((((d.W + hs - 1) / hs) + 7) / 8) * ((((d.H + vs - 1) / vs) + 7) / 8) * (hs * vs + 2);
     if (n > GPV_ENC_MAX_BLOCKS || blocks + n > GPV_ENC_MAX_TOTAL_BLOCKS) return hipErrorInvalidValue;
     blocks += n;
@@ -357,7 +419,10 @@ int gpv_enc_encode(gpv_enc_desc* descs, int B, int quality, int subsampling, voi
   R::write_header(h_T, Q, 0, 0, hs, vs, hdr.b);
   char* ws = (char*)workspace;
   const dim3 per_block((largest + COEF_THREADS - 1) / COEF_THREADS, B);
-  hipLaunchKernelGGL(gpv_enc_coef_kernel, per_block, dim3(COEF_THREADS), 0, s, ws, B, blocks, Q, hs, vs);
+  if (labelled)                                              // a call without labels runs the kernel without them
+    hipLaunchKernelGGL(gpv_enc_coef_kernel<true>, per_block, dim3(COEF_THREADS), 0, s, ws, B, blocks, Q, hs, vs);
+  else
+    hipLaunchKernelGGL(gpv_enc_coef_kernel<false>, per_block, dim3(COEF_THREADS), 0, s, ws, B, blocks, Q, hs, vs);
   hipLaunchKernelGGL(gpv_enc_offsets_kernel, dim3(B), dim3(IMG_THREADS), 0, s, ws, B, blocks, hs, vs);
   hipLaunchKernelGGL(gpv_enc_pack_kernel, per_block, dim3(COEF_THREADS), 0, s, ws, B, blocks, hs, vs);
   hipLaunchKernelGGL(gpv_enc_bytes_kernel, dim3(B), dim3(IMG_THREADS), 0, s, ws, B, blocks, hdr, out, capacity, sizes, status);

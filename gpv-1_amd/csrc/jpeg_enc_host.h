@@ -1,5 +1,5 @@
 // The JPEG encoding rule of gpv1_amd.jpeg_encode in plain C++ (no HIP): tables, header, colour, sampling, transform, quantiser and
-// the entropy code of one block.  jpeg_enc.hip compiles the same functions for the device (it defines GPV_ENC_FN as
+// the entropy code of one block, and the labels of the boxes (tools/label_host_check.cpp).  jpeg_enc.hip compiles the same functions for the device (it defines GPV_ENC_FN as
 // __host__ __device__ inline before including this file) and tools/enc_host_check.cpp includes it as it stands, so what the
 // stand-alone check proves about these functions holds for the kernels' arithmetic too.  DESIGN.md section 6h.
 #ifndef GPV_JPEG_ENC_HOST_H
@@ -268,6 +268,90 @@ GPV_ENC_FN void box_rect(const float* box, int H, int W, int* rect) {
 
 GPV_ENC_FN bool on_outline(const int* r, int x, int y) {
   return x >= r[0] && x <= r[2] && y >= r[1] && y <= r[3] && (x == r[0] || x == r[2] || y == r[1] || y == r[3]);
+}
+
+// The labels of the boxes (include/gpv_enc.h states the rule): a text of n <= MAX_LABEL characters in the 6 x 11 cell of the glyph
+// table, on a dark plate of (6 n + 2) x 13 pixels above or below its box.  Integers only.
+#include "jpeg_label_font.h"
+constexpr int MAX_LABEL = 32, CELL_W = 6, CELL_H = 11, PLATE_H = CELL_H + 2, PLATE_RGB = 10;
+
+struct Label {
+  int px, py;                 // the plate's top left corner
+  int n;                      // characters; 0 = the box has no label
+  int at;                     // where its text starts, in bytes behind the colours
+};
+
+// Box i's label from its length byte L (L & 0x7F characters, bit 7 = below the box) and `before` = the sum of the length bytes'
+// counts of the boxes in front of it; labels = the text bytes there are.  The count is clamped to MAX_LABEL and to the bytes that
+// remain, so that at + n <= labels whatever the length bytes hold.
+GPV_ENC_FN Label label_place(const int* rect, int L, int before, int labels, int H, int W) {
+  Label l;
+  l.at = before < labels ? before : labels;
+  l.n = L & 0x7F;
+  l.n = l.n < MAX_LABEL ? l.n : MAX_LABEL;
+  l.n = l.n < labels - l.at ? l.n : labels - l.at;
+  const int w = CELL_W * l.n + 2;
+  int py;
+  if (L & 0x80) {
+    py = rect[3] + 1;
+    if (py + PLATE_H > H) py = rect[3] - PLATE_H;
+  } else {
+    py = rect[1] - PLATE_H;
+    if (py < 0) py = rect[1] + 1;
+  }
+  const int top = H - PLATE_H > 0 ? H - PLATE_H : 0;
+  l.py = py < 0 ? 0 : py > top ? top : py;
+  int px = rect[0];
+  if (px + w > W) px = W - w;
+  l.px = px < 0 ? 0 : px;
+  return l;
+}
+
+GPV_ENC_FN bool on_plate(const Label& l, int x, int y) {
+  return l.n > 0 && x >= l.px && x < l.px + CELL_W * l.n + 2 && y >= l.py && y < l.py + PLATE_H;
+}
+
+// the glyph of a text byte: 0..94; a byte outside 32..126 is drawn as '?'
+GPV_ENC_FN int glyph_of(int byte) { return byte >= 32 && byte <= 126 ? byte - 32 : '?' - 32; }
+
+// of a pixel on the plate: ink (the box's colour) or plate.  glyph[k] = the glyph index (glyph_of) of the k-th text byte behind the
+// colours.  The pixel belongs to the cell of character c / 6; in its last column the NEXT character has the say where its row has
+// bit 7 (jpeg_label_font.h: Pillow pastes such a glyph one pixel to the left, over what the character before has left there).
+template <class G>
+GPV_ENC_FN bool label_ink(const Label& l, const LabelFont& font, const G& glyph, int x, int y) {
+  const int c = x - l.px - 1, r = y - l.py - 1;
+  if (c < 0 || c >= CELL_W * l.n || r < 0 || r >= CELL_H) return false;
+  const int k = c / CELL_W, j = c % CELL_W;
+  if (j == CELL_W - 1 && k + 1 < l.n) {
+    const int next = font.rows[glyph[l.at + k + 1]][r];
+    if (next & 0x80) return (next >> 6) & 1;
+  }
+  return (font.rows[glyph[l.at + k]][r] >> j) & 1;
+}
+
+// The labels of one picture drawn into rgb[H][pitch][3] over the outlines, in box order: rects = nboxes x (x1, y1, x2, y2) of box_rect,
+// colours = nboxes x 4 bytes (R, G, B, length byte) with `labels` text bytes behind them.  false: arguments outside the rule's extents.
+inline bool draw_labels(uint8_t* rgb, int H, int W, int pitch, const int* rects, const uint8_t* colours, int nboxes, int labels) {
+  if (!rgb || H < 1 || W < 1 || pitch < W || nboxes < 0 || nboxes > MAX_BOXES || labels < 0 || labels > nboxes * MAX_LABEL ||
+      (nboxes && (!rects || !colours)))
+    return false;
+  static constexpr LabelFont font = make_label_font();
+  const uint8_t* text = colours + 4 * nboxes;
+  uint8_t glyph[MAX_BOXES * MAX_LABEL];
+  for (int k = 0; k < labels; ++k) glyph[k] = (uint8_t)glyph_of(text[k]);
+  int before = 0;
+  for (int i = 0; i < nboxes; ++i) {
+    const int L = colours[4 * i + 3];
+    const Label l = label_place(rects + 4 * i, L, before, labels, H, W);
+    before += L & 0x7F;
+    for (int y = l.py < 0 ? 0 : l.py; y < H && y < l.py + PLATE_H; ++y)
+      for (int x = l.px < 0 ? 0 : l.px; x < W && on_plate(l, x, y); ++x) {
+        const bool ink = label_ink(l, font, glyph, x, y);
+        uint8_t* p = rgb + ((size_t)y * pitch + x) * 3;
+        for (int ch = 0; ch < 3; ++ch) p[ch] = ink ? colours[4 * i + ch] : (uint8_t)PLATE_RGB;
+      }
+  }
+  return true;
 }
 
 // std * x, + mean, * 255, + 0.5, floor, clamp to 0..255 (a NaN gives 0); fp32, every operation on its own

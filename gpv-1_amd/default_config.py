@@ -89,6 +89,7 @@ _TREE = {'exp_name': 'default',
               'prefetch': 1,                       # batches the loader's worker thread prepares ahead (data_source: files)
               'vis_step': 2000,
               'visualize': 'off',                  # 'device': training visualisations every vis_step steps (gpv1_amd.visualize)
+              'vis_labels': False,                 # scores above the predicted boxes, `GT` below the ground truth (visualize(labels=True))
               'log_step': 10,
               'ckpt_step': 2000,
               'lr': 0.0001,

@@ -14,6 +14,7 @@ EXPORTS = ['gpv_enc_encode', 'gpv_enc_header', 'gpv_enc_workspace_bytes']
 SRC_U8, SRC_BF16, SRC_F32 = 0, 1, 2                       # GPV_ENC_SRC_*
 SUBSAMPLING = {'4:4:4': 0, '4:2:2': 1, '4:2:0': 2}        # GPV_ENC_4xx
 MAX_BOXES, MAX_BLOCKS, MAX_TOTAL_BLOCKS = 32, 1 << 20, 1 << 24
+MAX_LABEL = 32                                            # characters of one box's label
 HEADER_BYTES, BLOCK_BYTES, STATUS_CAPACITY = 623, 208, 1
 _LIB = None
 _LIB_PATH = _native.lib_path('enc')
@@ -22,7 +23,7 @@ _LIB_PATH = _native.lib_path('enc')
 class EncDesc(C.Structure):
     _fields_ = [('src', C.c_void_p), ('boxes', C.c_void_p), ('colours', C.c_void_p), ('H', C.c_int), ('W', C.c_int), ('pitch', C.c_int),
                 ('kind', C.c_int), ('nboxes', C.c_int), ('mean', C.c_float * 3), ('std', C.c_float * 3), ('block_base', C.c_int),
-                ('nblocks', C.c_int), ('reserved', C.c_int)]
+                ('nblocks', C.c_int), ('labels', C.c_int)]
 
 
 _SIGNATURES = {'gpv_enc_workspace_bytes': [C.c_int, C.c_int64, C.POINTER(C.c_int64)],
@@ -82,6 +83,8 @@ def encode(descs, B, quality, subsampling, workspace, out, capacity, sizes, stat
         if not (1 <= d.H <= 65535 and 1 <= d.W <= 65535 and d.pitch >= d.W and 0 <= d.nboxes <= MAX_BOXES):
             raise ValueError(f'hip_enc.encode: picture {i}: H and W must be 1..65535, pitch >= W and at most {MAX_BOXES} boxes, got '
                              f'{d.H} x {d.W}, pitch {d.pitch}, {d.nboxes} boxes')
+        if not 0 <= d.labels <= d.nboxes * MAX_LABEL:
+            raise ValueError(f'hip_enc.encode: picture {i}: at most {MAX_LABEL} label bytes per box, got {d.labels} for {d.nboxes} boxes')
         n = block_count(d.H, d.W, subsampling)
         if n > MAX_BLOCKS:
             raise ValueError(f'hip_enc.encode: picture {i} has {n} blocks, at most {MAX_BLOCKS} are supported')

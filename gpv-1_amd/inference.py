@@ -14,9 +14,10 @@ usage: python -m gpv1_amd.inference [--config some.yaml] ckpt=... inputs.img=img
                                       [beam.impl=device] [beam.finished=freeze] [beam.length_penalty=0.6]
                                       [inputs.answers="cat|dog|traffic light"]
                                       [sample.num=3] [sample.temperature=0.8] [sample.top_k=20] [sample.top_p=0.9] [sample.seed=1]
-                                      [outputs.vis=picture.jpg]
+                                      [outputs.vis=picture.jpg] [outputs.vis_labels=true]
 ``outputs.vis`` (the reference's ``inference_util.vis_sample``): the picture the model saw with the ``num_output_boxes`` boxes drawn,
-encoded on the device (gpv1_amd.jpeg_encode.DeviceJpegEncoder) and written to that path.
+encoded on the device (gpv1_amd.jpeg_encode.DeviceJpegEncoder) and written to that path.  With ``outputs.vis_labels=true`` every
+box carries its relevance score and the predicted answer stands in the picture's top left corner (``vis_lists``).
 """
 import argparse
 import os
@@ -177,14 +178,35 @@ def predict(model, images, queries, beam_size=None, num_output_boxes=None, size=
     return decode_outputs(out, model, num_output_boxes)
 
 
-def write_vis(path, image, boxes, device, colour=(255, 0, 0)):
+FRAME_BOX, FRAME_COLOUR = (0.5, 0.5, 1.0, 1.0), (255, 255, 255)       # the whole picture: the box that carries the answer
+
+
+def vis_lists(boxes, relevance=None, answer=None, colour=(255, 0, 0)):
+    """boxes, colours and labels of write_vis in drawing order.  With `relevance` every box carries its score, two decimals, above
+    it (the reference's vis_sample); with `answer` a white box around the whole picture is drawn first and carries the answer: its
+    frame is the picture's border, so the text lands inside the top left corner (cut to 32 characters like every label).
+    -> (boxes [n, 4], colours, labels or None)"""
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    colours = [colour] * len(boxes)
+    if relevance is None and answer is None:
+        return boxes, colours, None
+    labels = [None] * len(boxes) if relevance is None else [f'{float(s):.2f}' for s in relevance]
+    if len(labels) != len(boxes):
+        raise ValueError(f'write_vis: one relevance score per box, got {len(labels)} for {len(boxes)} boxes')
+    if answer is not None:
+        boxes, colours, labels = np.concatenate([np.asarray([FRAME_BOX], np.float32), boxes]), [FRAME_COLOUR] + colours, [str(answer)] + labels
+    return boxes, colours, labels
+
+
+def write_vis(path, image, boxes, device, colour=(255, 0, 0), relevance=None, answer=None):
     """the picture as preprocess_image hands it to the model, with `boxes` ([n, 4] normalised cx, cy, w, h) outlined -> a JPEG file
-    at `path`, denormalised, drawn and encoded on the device"""
+    at `path`, denormalised, drawn and encoded on the device.  relevance / answer: labels, see vis_lists."""
     from .jpeg_encode import DeviceJpegEncoder
     from .visualize import stem_layout
     nested = stem_layout(nested_tensor_from_tensor_list([preprocess_image(image).to(device)]))
-    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
-    data = DeviceJpegEncoder(device=device).encode_batch(nested, IMAGENET_MEAN, IMAGENET_STD, boxes=[boxes], colours=[[colour] * len(boxes)])[0]
+    boxes, colours, labels = vis_lists(boxes, relevance, answer, colour)
+    data = DeviceJpegEncoder(device=device).encode_batch(nested, IMAGENET_MEAN, IMAGENET_STD, boxes=[boxes], colours=[colours],
+                                                         **({} if labels is None else {'labels': [labels]}))[0]
     with open(path, 'wb') as f:
         f.write(data)
 
@@ -194,7 +216,7 @@ def main(argv=None):
     ap.add_argument('--config', default=None, help='YAML file (e.g. the reference configs/exp/gpv.yaml); default: gpv1_amd.default_config')
     ap.add_argument('overrides', nargs='*')
     args = ap.parse_args(argv)
-    # outputs.vis= ckpt= inputs.img= inputs.query= inputs.answers= beam_size= beam.impl= beam.finished= beam.length_penalty=
+    # outputs.vis= outputs.vis_labels= ckpt= inputs.img= inputs.query= inputs.answers= beam_size= beam.impl= beam.finished= beam.length_penalty=
     # beam.no_repeat_ngram= beam.min_length= beam.repetition_penalty= sample.num= sample.temperature= sample.top_k= sample.top_p=
     # sample.seed= are added keys
     cfg = load_config(args.config, args.overrides, strict=False) if args.config else from_dict(default_tree(), args.overrides, strict=False)
@@ -210,9 +232,12 @@ def main(argv=None):
         print(k)
         print('-' * 80)
         print(v)
-    vis = (cfg.get('outputs', None) or {}).get('vis', None)
+    outputs = cfg.get('outputs', None) or {}
+    vis = outputs.get('vis', None)
     if vis:
-        write_vis(str(vis), img, pred['boxes'], 'cuda:0')
+        labelled = bool(outputs.get('vis_labels', False))        # outputs.vis_labels=true: scores on the boxes, the answer on the picture
+        write_vis(str(vis), img, pred['boxes'], 'cuda:0', relevance=pred['relevance'] if labelled else None,
+                  answer=pred['answer'] if labelled else None)
         print('-' * 80)
         print('wrote', vis)
 

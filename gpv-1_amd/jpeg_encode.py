@@ -5,6 +5,8 @@ gpv-1_amd/csrc/jpeg_enc.hip on the device, byte for byte.  DESIGN.md section 6h.
 slow-integer DCT, the Annex K tables, no optimisation): a baseline sequential JPEG, 8 bit, three components, one interleaved scan,
 no restart markers.  ``draw_boxes_host`` and ``denormalise_host`` are the two rules in front of it: the one-pixel box outlines of
 the reference's ``vis_bbox(..., modify=True, alpha=0)`` and the way from a normalised pipeline batch back to uint8.
+``label_plates`` / ``draw_labels_host`` state the labels of the boxes (the reference's ``vis.add_box``): a short text in Pillow's
+built-in bitmap font on a dark plate above or below its box, the pixels Pillow's ``rectangle`` + ``text`` draw.
 """
 import numpy as np
 
@@ -271,6 +273,106 @@ def draw_boxes_host(img, boxes_ncxcywh, colours):
     return img
 
 
+MAX_LABEL, CELL_W, CELL_H, PLATE_H, PLATE_RGB = 32, 6, 11, 13, (10, 10, 10)
+
+
+def label_entries(labels, n):
+    """the labels of one picture's n boxes -> [(text bytes, below)]: an entry is None (no label), a str (above the box) or
+    (str, 'above' | 'below').  A character outside ASCII 32..126 becomes '?', a longer text is cut to MAX_LABEL characters."""
+    if labels is None:
+        return [(b'', False)] * n
+    if len(labels) != n:
+        raise ValueError(f'labels: one entry per box is needed (None for a box without label), got {len(labels)} entries for {n} boxes')
+    out = []
+    for e in labels:
+        text, where = (e, 'above') if e is None or isinstance(e, str) else e
+        if not (text is None or isinstance(text, str)) or where not in ('above', 'below'):
+            raise ValueError(f"labels: an entry is None, a str or (str, 'above' | 'below'), got {e!r}")
+        text = bytes(ord(c) if 32 <= ord(c) <= 126 else ord('?') for c in (text or '')[:MAX_LABEL])
+        out.append((text, where == 'below'))
+    return out
+
+
+def label_plates(boxes_ncxcywh, labels, H, W):
+    """-> int rows (px, py, n), one per box: the top left corner of the label's plate and its character count (0: no label, nothing
+    is drawn).  The plate is 6 n + 2 wide and 13 high.  Above the box, or inside it under its top edge where there is no room above;
+    below, or inside over its bottom edge; kept inside the picture where it fits, left-aligned with the box."""
+    rects = box_rects(boxes_ncxcywh, H, W)
+    out = []
+    for (x1, y1, x2, y2), (text, below) in zip(rects.tolist(), label_entries(labels, len(rects))):
+        w = CELL_W * len(text) + 2
+        if below:
+            py = y2 + 1
+            if py + PLATE_H > H:
+                py = y2 - PLATE_H
+        else:
+            py = y1 - PLATE_H
+            if py < 0:
+                py = y1 + 1
+        py = min(max(py, 0), max(0, H - PLATE_H))
+        px = x1
+        if px + w > W:
+            px = W - w
+        px = max(px, 0)
+        out.append((px, py, len(text)))
+    return np.array(out, np.int64).reshape(-1, 3)
+
+
+def draw_labels_host(img, boxes_ncxcywh, colours, labels):
+    """writes the labels of the boxes into img (uint8 [H, W, 3], modified in place and returned), after draw_boxes_host and in the
+    order given: a later label overwrites an earlier one, and no outline cuts a label.  labels: see label_entries.  The text is
+    inked in the box's colour, in the 6 x 11 cell of jpeg_label_font, on a plate of PLATE_RGB with one pixel of margin all round."""
+    from .jpeg_label_font import ROWS
+    H, W = img.shape[:2]
+    colours = np.asarray(colours, np.uint8).reshape(-1, 3)
+    plates = label_plates(boxes_ncxcywh, labels, H, W)
+    if len(plates) != len(colours) or len(plates) > MAX_BOXES:
+        raise ValueError(f'draw_labels_host: one colour per box and at most {MAX_BOXES} boxes, got {len(plates)} boxes, {len(colours)} colours')
+    for (px, py, n), (text, _), colour in zip(plates.tolist(), label_entries(labels, len(plates)), colours):
+        if n == 0:
+            continue
+        plate = np.empty((PLATE_H, CELL_W * n + 2, 3), np.uint8)
+        plate[:] = PLATE_RGB
+        ink = np.zeros((CELL_H, CELL_W * n), bool)
+        for k, byte in enumerate(text):                      # as Pillow pastes them: one after the other, each over what is there
+            rows = np.array(ROWS[byte - 32], np.uint8)
+            ink[:, CELL_W * k:CELL_W * (k + 1)] = (rows[:, None] >> np.arange(CELL_W)[None, :]) & 1
+            if k:                                            # a glyph that starts one pixel left of its cell (bit 7), ink or not (bit 6)
+                left = ink[:, CELL_W * k - 1]
+                left[rows & 0x80 != 0] = (rows[rows & 0x80 != 0] & 0x40) != 0
+        plate[1:1 + CELL_H, 1:-1][ink] = colour
+        view = img[py:py + PLATE_H, px:px + plate.shape[1]]                 # the picture's edges clip the plate
+        view[:] = plate[:view.shape[0], :view.shape[1]]
+    return img
+
+
+def pack_labels(colours, labels):
+    """what the device reads at gpv_enc_desc.colours (include/gpv_enc.h): n x (R, G, B, L) and the texts behind them -> (uint8
+    array, text bytes).  L = the character count, + 0x80 for a label below its box."""
+    colours = np.asarray(colours, np.uint8).reshape(-1, 3)
+    entries = label_entries(labels, len(colours))
+    head = np.concatenate([colours, np.array([[len(t) | (0x80 if below else 0)] for t, below in entries], np.uint8).reshape(-1, 1)], 1)
+    text = b''.join(t for t, _ in entries)
+    return np.concatenate([head.reshape(-1), np.frombuffer(text, np.uint8)]), len(text)
+
+
+def unpack_labels(packed, nboxes, nbytes):
+    """the way back, as the device reads it: -> (colours [n, 3], labels as label_entries takes them).  The length bytes are not
+    trusted: box i's text starts at min(sum of the counts in front of it, nbytes), and its count is clamped to MAX_LABEL and to
+    the bytes that remain behind that."""
+    packed = np.asarray(packed, np.uint8).reshape(-1)
+    if not 0 <= nbytes <= nboxes * MAX_LABEL or len(packed) < 4 * nboxes + nbytes:
+        raise ValueError(f'unpack_labels: {nboxes} boxes with {nbytes} text bytes need {4 * nboxes + nbytes} bytes and at most {MAX_LABEL} per box, got {len(packed)}')
+    head, text = packed[:4 * nboxes].reshape(-1, 4), packed[4 * nboxes:4 * nboxes + nbytes].tobytes()
+    labels, before = [], 0
+    for L in head[:, 3].tolist():
+        at = min(before, nbytes)
+        n = min(L & 0x7F, MAX_LABEL, nbytes - at)
+        before += L & 0x7F
+        labels.append((''.join(chr(c) for c in text[at:at + n]), 'below' if L & 0x80 else 'above'))
+    return head[:, :3].copy(), labels
+
+
 def denormalise_host(x, mean, std):
     """x: [..., 3] normalised pixels (fp32 array, or a bf16 / fp32 tensor) -> uint8.  Per channel in fp32, every operation rounded
     on its own: std * x, + mean, * 255, + 0.5, floor, clamp to 0..255 (a NaN gives 0)."""
@@ -304,21 +406,34 @@ class DeviceJpegEncoder:
             t = self._buffers[name] = torch.empty(n, dtype=dtype, device=self.device)
         return t[:n]
 
-    def _boxes(self, descs, boxes, colours, keep):
+    def _boxes(self, descs, boxes, colours, keep, labels=None):
         import torch
         if boxes is None:
+            if labels is not None:
+                raise ValueError('DeviceJpegEncoder: labels belong to boxes, and there are none')
             return
         if colours is None or len(boxes) != len(descs) or len(colours) != len(descs):
             raise ValueError('DeviceJpegEncoder: boxes and colours are lists with one entry per picture')
-        for d, b, c in zip(descs, boxes, colours):
+        if labels is not None and len(labels) != len(descs):
+            raise ValueError(f'DeviceJpegEncoder: labels is a list with one entry per picture, got {len(labels)} for {len(descs)} pictures')
+        for i, (d, b, c) in enumerate(zip(descs, boxes, colours)):
             b = torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4)
             c = torch.as_tensor(c, dtype=torch.uint8).reshape(-1, 3)
             if len(b) != len(c) or len(b) > MAX_BOXES:
                 raise ValueError(f'DeviceJpegEncoder: one colour per box and at most {MAX_BOXES} boxes per picture, got {len(b)} boxes, {len(c)} colours')
-            if len(b) == 0:
+            if labels is not None and labels[i] is not None:
+                # colours, length bytes and texts in the one tensor that is uploaded anyway (include/gpv_enc.h: Storage)
+                packed, nbytes = pack_labels(c.cpu().numpy(), labels[i])             # (a list that does not match the boxes raises)
+                if len(b) == 0:
+                    continue
+                c = torch.from_numpy(packed)
+                d.labels = nbytes
+            elif len(b) == 0:
                 continue
+            else:
+                c = torch.cat([c, c[:, :1]], 1)
             b = b.to(self.device).contiguous()
-            c = torch.cat([c, c[:, :1]], 1).to(self.device).contiguous()
+            c = c.to(self.device).contiguous()
             keep += [b, c]
             d.boxes, d.colours, d.nboxes = b.data_ptr(), c.data_ptr(), len(b)
 
@@ -353,9 +468,11 @@ class DeviceJpegEncoder:
         ends = np.cumsum(n)
         return [used[e - k:e] for e, k in zip(ends, n)]
 
-    def encode(self, images, boxes=None, colours=None):
+    def encode(self, images, boxes=None, colours=None, labels=None):
         """images: list of uint8 [H, W, 3] tensors or arrays of any sizes; a device tensor that is a window of a larger picture
-        (rows `pitch` pixels apart) is read in place.  boxes / colours: per picture, [n, 4] normalised (cx, cy, w, h) and [n, 3]."""
+        (rows `pitch` pixels apart) is read in place.  boxes / colours: per picture, [n, 4] normalised (cx, cy, w, h) and [n, 3].
+        labels: per picture, None or a list with one entry per box: None, a str (drawn above the box) or (str, 'above' | 'below');
+        a text is cut to 32 characters and a character outside ASCII 32..126 becomes '?' (label_entries, draw_labels_host)."""
         import torch
         from . import hip_enc
 
@@ -371,12 +488,13 @@ class DeviceJpegEncoder:
                     t = t.contiguous()
                 keep.append(t)
                 d.src, d.H, d.W, d.pitch, d.kind = t.data_ptr(), t.shape[0], t.shape[1], t.stride(0) // 3, hip_enc.SRC_U8
-            self._boxes(descs, boxes, colours, keep)
+            self._boxes(descs, boxes, colours, keep, labels)
         return self._run(len(images), fill)
 
-    def encode_batch(self, nested, mean, std, boxes=None, colours=None, count=None):
+    def encode_batch(self, nested, mean, std, boxes=None, colours=None, count=None, labels=None):
         """the first `count` pictures (default: all) of a pipeline batch: nested.tensors = the stem's padded NHWC4 batch
-        [B, H + 6, Wp, 4] in bf16 or fp32, nested.mask = [B, H, W]; mean, std = the three normalisation constants each"""
+        [B, H + 6, Wp, 4] in bf16 or fp32, nested.mask = [B, H, W]; mean, std = the three normalisation constants each; labels as
+        in encode"""
         import torch
         from . import hip_enc
         x = nested.tensors
@@ -395,5 +513,6 @@ class DeviceJpegEncoder:
                 d.src = x.data_ptr() + ((i * Hp + self.PAD) * Wp + self.PAD) * 4 * x.element_size()
                 d.H, d.W, d.pitch, d.kind = H, W, Wp, hip_enc.SRC_BF16 if x.dtype == torch.bfloat16 else hip_enc.SRC_F32
                 d.mean[:], d.std[:] = [float(v) for v in mean], [float(v) for v in std]
-            self._boxes(descs, None if boxes is None else boxes[:B], None if colours is None else colours[:B], keep)
+            self._boxes(descs, None if boxes is None else boxes[:B], None if colours is None else colours[:B], keep,
+                        None if labels is None else labels[:B])
         return self._run(B, fill)

@@ -30,7 +30,9 @@ What is reproduced -- everything between the data loader and the checkpoint file
     writes ``exp_dir/training_visualizations/<subset>_<step>/`` for ``train`` and ``val`` -- the first
     ``training.num_vis_samples`` pictures as the model saw them, boxes drawn and JPEG-encoded on the device
     (gpv1_amd.visualize, csrc/jpeg_enc.hip), and an ``index.html``.  Between steps, outside any graph capture; the batches come from
-    the evaluation datasets (``train`` falls back to the training dataset's first batches when there are none).
+    the evaluation datasets (``train`` falls back to the training dataset's first batches when there are none).  The added key
+    ``training.vis_labels: true`` (default false) writes each predicted box's relevance score above it and ``GT`` below each
+    ground-truth box, on the device as well.
 Out of scope: dataset ETL (downloading / preprocessing COCO; READING what it wrote is gpv1_amd.datasets), TensorBoard.  Without ``eval_datasets`` this driver checkpoints every
 ``training.ckpt_step`` steps and at every epoch end into ``model.pth``.
 The dataset is any sequence of ``(image[3,H,W] fp32 normalised, query str | (ids, mask), target dict)``;
@@ -234,7 +236,8 @@ def visualize_subsets(model, cfg, step, dataset, eval_datasets, batch_size, devi
         if not sets:
             continue
         log(f'Visualizing {subset} ...')
-        visualize(model, itertools.chain.from_iterable(eval_batches(ds, batch_size, device) for ds in sets), cfg, step, subset)
+        visualize(model, itertools.chain.from_iterable(eval_batches(ds, batch_size, device) for ds in sets), cfg, step, subset,
+                  labels=bool(cfg.training.get('vis_labels', False)))
 
 
 def save_checkpoint(path, model, trainer, epoch, step, metric=0.0):

@@ -52,6 +52,14 @@ def box_lists(pred_boxes, order, gt_boxes):
     return torch.cat(parts), colours
 
 
+def label_lists(scores, n_gt):
+    """the labels of one sample's boxes in the drawing order of box_lists: every predicted box carries its relevance score, two
+    decimals, above it, every ground-truth box `GT` below it (the reference's vis.add_box).  scores = the top-5 values, best first."""
+    k = min(n_gt, TOP_K)
+    order = list(range(k, TOP_K)) + list(range(k))
+    return [f'{float(scores[i]):.2f}' for i in order] + [('GT', 'below')] * min(n_gt, jpeg_encode.MAX_BOXES - TOP_K)
+
+
 def stem_layout(nested):
     """the batch in the stem's padded NHWC4 layout: the device loader's batches are in it already"""
     x = nested.tensors
@@ -78,10 +86,12 @@ def _host_pictures(nested, count):
 
 
 @torch.no_grad()
-def visualize(model, batches, cfg, step, subset, encoder=None):
+def visualize(model, batches, cfg, step, subset, encoder=None, labels=False):
     """batches: an iterable of (images, queries, targets) as the evaluators read them.  encoder: None = a DeviceJpegEncoder on the
     model's device (quality 90, 4:2:0); or a callable picture -> bytes (uint8 [H, W, 3] array in, e.g. jpeg_encode.encode_host), for
-    which the pictures are built on the host by denormalise_host and draw_boxes_host.  Leaves the model in the mode it was in.
+    which the pictures are built on the host by denormalise_host, draw_boxes_host and draw_labels_host.  labels: every predicted
+    box carries its relevance score above it and every ground-truth box `GT` below it (label_lists); with either encoder.  Leaves
+    the model in the mode it was in.
     -> the directory written"""
     dev = model.vision_token.device
     vis_dir = os.path.join(cfg.exp_dir, 'training_visualizations', f'{subset}_{step:06d}')
@@ -105,11 +115,17 @@ def visualize(model, batches, cfg, step, subset, encoder=None):
             pred_answers = model.token_ids_to_words(top1)
             take = min(prob.shape[0], limit - count)
             boxes, colours = zip(*[box_lists(outputs['pred_boxes'][b], top.indices[b], targets[b].get('boxes')) for b in range(take)])
+            values = top.values.detach().cpu().numpy()         # for index.html, and for the labels: one copy serves both
+            n_gt = [0 if targets[b].get('boxes') is None else int(targets[b]['boxes'].shape[0]) for b in range(take)]
+            tags = [label_lists(values[b], n_gt[b]) for b in range(take)] if labels else None
             if hasattr(encoder, 'encode_batch'):
-                files = encoder.encode_batch(stem_layout(nested), IMAGENET_MEAN, IMAGENET_STD, boxes=list(boxes), colours=list(colours), count=take)
+                files = encoder.encode_batch(stem_layout(nested), IMAGENET_MEAN, IMAGENET_STD, boxes=list(boxes), colours=list(colours), count=take,
+                                             **({'labels': tags} if labels else {}))
             else:
-                files = [encoder(jpeg_encode.draw_boxes_host(p, b.cpu().numpy(), c)) for p, b, c in zip(_host_pictures(nested, take), boxes, colours)]
-            values = top.values.detach().cpu().numpy()
+                files = []
+                for i, (p, b, c) in enumerate(zip(_host_pictures(nested, take), boxes, colours)):
+                    p = jpeg_encode.draw_boxes_host(p, b.cpu().numpy(), c)
+                    files.append(encoder(jpeg_encode.draw_labels_host(p, b.cpu().numpy(), c, tags[i]) if labels else p))
             texts = queries if isinstance(queries, (list, tuple)) and all(isinstance(q, str) for q in queries) else None   # else (ids, mask)
             for b in range(take):
                 name = f'{step:06d}_{count + b:04d}.jpg'

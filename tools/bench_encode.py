@@ -5,7 +5,9 @@
   (c) the loader-fed bs32 train step (tools/bench_loader.py's tree) with training visualisations every 50 steps against none: 100
       steps each, alternating, and what one visualize() call of 15 samples costs.
 Warm-up first, five runs each, median and spread reported.  One JSON document on stdout.
-usage: python tools/bench_encode.py [--no-step] [--steps 100] [--vis-step 50]      (GPU box)"""
+--labels N: (a) with N labelled boxes per picture (labels); --device-only --lib PATH: (a) alone through another build of
+libgpv_enc.so, one process per run, for interleaved comparisons of two builds (profiles/r21_labels.txt).
+usage: python tools/bench_encode.py [--no-step] [--steps 100] [--vis-step 50] [--labels N] [--device-only [--lib PATH]]      (GPU box)"""
 import argparse
 import io
 import json
@@ -51,17 +53,21 @@ def wall(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-def encode_numbers(n):
+def encode_numbers(n, labels=0, host=True, bare=5):
+    """labels = 0: `bare` boxes per picture without labels; labels = N: N boxes per picture, each with a label (a score above or `GT` below)"""
     imgs = pictures(n)
     nested = DeviceImagePipeline(train=False)(imgs)
     rng = np.random.default_rng(1)
-    boxes = [np.concatenate([rng.uniform(0.3, 0.7, (5, 2)), rng.uniform(0.1, 0.5, (5, 2))], 1).astype(np.float32) for _ in range(n)]
-    colours = [[(255, 0, 0)] * 5 for _ in range(n)]
+    nb = labels or bare
+    boxes = [np.concatenate([rng.uniform(0.3, 0.7, (nb, 2)), rng.uniform(0.1, 0.5, (nb, 2))], 1).astype(np.float32) for _ in range(n)]
+    colours = [[(255, 0, 0)] * nb for _ in range(n)]
+    texts = [[f'{rng.uniform():.2f}' if k % 2 == 0 else ('GT', 'below') for k in range(nb)] for _ in range(n)] if labels else None
     enc = jpeg_encode.DeviceJpegEncoder(quality=90, subsampling='4:2:0')
-    run = lambda: enc.encode_batch(nested, IMAGENET_MEAN, IMAGENET_STD, boxes=boxes, colours=colours)
+    run = lambda: enc.encode_batch(nested, IMAGENET_MEAN, IMAGENET_STD, boxes=boxes, colours=colours, **({'labels': texts} if labels else {}))
     files = run()
     run()
-    res = {'pictures': n, 'file_bytes_mean': float(np.mean([len(f) for f in files])), 'device_end_to_end': stats([wall(run) for _ in range(RUNS)])}
+    res = {'pictures': n, 'boxes_per_picture': nb, 'labels_per_picture': labels, 'library': hip_enc._LIB_PATH,
+           'file_bytes_mean': float(np.mean([len(f) for f in files])), 'device_end_to_end': stats([wall(run) for _ in range(RUNS)])}
     # the four launches alone: the raw entry point between two events, descriptors as encode_batch fills them
     import ctypes as C
     x = nested.tensors
@@ -73,9 +79,10 @@ def encode_numbers(n):
         d.src = x.data_ptr() + ((i * Hp + 3) * Wp + 3) * 4 * x.element_size()
         d.H, d.W, d.pitch, d.kind = 480, 640, Wp, hip_enc.SRC_BF16 if x.dtype == torch.bfloat16 else hip_enc.SRC_F32
         d.mean[:], d.std[:] = IMAGENET_MEAN, IMAGENET_STD
-        b, c = torch.as_tensor(boxes[i]).cuda(), torch.tensor([[255, 0, 0, 0]] * 5, dtype=torch.uint8).cuda()
+        packed, nbytes = jpeg_encode.pack_labels(colours[i], texts[i] if labels else None)
+        b, c = torch.as_tensor(boxes[i]).cuda(), torch.from_numpy(packed).cuda()
         keep += [b, c]
-        d.boxes, d.colours, d.nboxes = b.data_ptr(), c.data_ptr(), 5
+        d.boxes, d.colours, d.nboxes, d.labels = b.data_ptr(), c.data_ptr(), nb, nbytes
     count = hip_enc.block_count(480, 640, '4:2:0')
     capacity = (hip_enc.HEADER_BYTES + 2 + 64 * count + 15) & ~15
     ws = torch.empty(hip_enc.workspace_bytes(n, n * count), dtype=torch.uint8, device='cuda')
@@ -94,6 +101,8 @@ def encode_numbers(n):
         e1.synchronize()
         ms.append(e0.elapsed_time(e1) / 10)
     res['device_four_launches'] = stats(ms)
+    if not host:
+        return res
     # (b) the pictures as uint8 on the device (what a host encoder would be handed), copied back and encoded by Pillow
     from PIL import Image
     dev_u8 = torch.stack([torch.from_numpy(jpeg_encode.denormalise_host(x[i, 3:483, 3:643, :3].cpu(), IMAGENET_MEAN, IMAGENET_STD)) for i in range(n)]).cuda()
@@ -175,8 +184,17 @@ def main():
     ap.add_argument('--no-step', action='store_true', help='(a) and (b) only')
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--vis-step', type=int, default=50)
+    ap.add_argument('--labels', type=int, default=0, help='(a) with N labelled boxes per picture instead of five bare ones')
+    ap.add_argument('--device-only', action='store_true', help='(a) only, at 32 pictures')
+    ap.add_argument('--boxes', type=int, default=5, help='with --device-only and without --labels: bare boxes per picture')
+    ap.add_argument('--lib', default=None, help='(a) through another libgpv_enc.so, e.g. one built from the parent commit (same ABI, no labels)')
     a = ap.parse_args()
-    res = {'encode': [encode_numbers(n) for n in (15, 32)]}
+    if a.lib:
+        hip_enc._LIB_PATH = os.path.abspath(a.lib)
+    if a.device_only:
+        print(json.dumps(encode_numbers(32, a.labels, host=False, bare=a.boxes)))
+        return
+    res = {'encode': [encode_numbers(n, a.labels) for n in (15, 32)]}
     if not a.no_step:
         res['train_step'] = step_numbers(a)
     print(json.dumps(res, indent=1))
